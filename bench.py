@@ -2,6 +2,12 @@
 """Benchmark of the MI355X batched SHA-256 hash path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c3dd|c4|c5] [--mode kernel|lib]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps, writes the last step's digests
+if --dump-outputs is given and prints the line. Everything else below that takes
+runs of its own -- the oracle spot-check of the timed output, the clock probe
+(clock_after), extra_configs, cpu_baseline, host_api -- runs only with --full.
 
 A *step* is one pass of the hot path -- processor.ProcessHashActions
 (/root/reference/pkg/processor/serial.go:180-198) over one batch of synthetic
@@ -12,12 +18,12 @@ quoted on). N>1: one process per GPU (torchrun; started by this script itself
 when WORLD_SIZE is unset), every rank hashes its own disjoint 2^20-request
 slice (weak scaling, no collective on the data path); the timed region is
 bracketed by barrier + synchronize and the max over ranks is taken. Rank 0
-prints ONE JSON line. With --config c2 on one GPU the line also carries
+prints ONE JSON line. With --full --config c2 on one GPU the line also carries
 extra_configs (c3, c4 and c5 timed the same way, each with its own roofline
 fraction and verified sample). --mode lib instead times the north-star host
 path in ONE process: one libmirsha context over N GPUs (device_mask), a pinned
 arena, msha_digest_batch per step (PCIe-inclusive; never the headline value); the
-default run reports it as host_api (c5 over all N GPUs, a child process). Warmup: the W steps, then more untimed
+--full run reports it as host_api (c5 over all N GPUs, a child process). Warmup: the W steps, then more untimed
 steps until --min-warmup-ms (300) of wall time has passed -- MI355X clocks need
 ~100 ms of load to settle, and a cold timed region measures the clock ramp
 (c2: 0.395 ms per launch after 3 warmup steps, 0.330 ms after 200); the line
@@ -83,6 +89,16 @@ def parse():
                         "N uniform messages via the batch kernel) | "
                         "u:N:SIZE[:STRIDE] (experiment: N uniform messages via the uniform kernel; "
                         "STRIDE 0 makes every lane hash the same cached message)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline's timed steps, also run everything else the benchmark measures "
+                        "or checks: the oracle spot-check of the timed output, the clock probe, "
+                        "extra_configs, cpu_baseline and the host_api legs (each still has its --no-* switch). "
+                        "Without it a run sets up, warms up, times the K steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the digests the last timed step left in the caller's "
+                        "output array to DIR/digests.npy (float32, one row of 32 byte values per digest; "
+                        "DIR/digests_rank<R>.npy per rank with --gpus N > 1). More than DUMP_MAX_ROWS "
+                        "digests: a fixed, seeded sample of rows, the same from run to run")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--policy", default="auto", choices=["auto", "lane", "coop"],
@@ -101,7 +117,7 @@ def parse():
                    help="with --mode lib --config c5: every action packs its own copy of its payload, in "
                         "action order (a caller that does not share EpochChange payloads between actions)")
     p.add_argument("--no-extra", action="store_true",
-                   help="skip the extra_configs legs (one GPU: c3, c4, c5; N GPUs: c5 over all ranks)")
+                   help="with --full: skip the extra_configs legs (one GPU: c3, c4, c5; N GPUs: c5 over all ranks)")
     p.add_argument("--no-host-api", action="store_true",
                    help="skip the host_api legs (c5 through msha_digest_batch over all N GPUs, one process)")
     p.add_argument("--no-host-api-unaliased", action="store_true",
@@ -249,6 +265,33 @@ def verify_sample(w, d_out, k: int = 512) -> None:
     exp = oracle.digest_batch(w.arena, w.off[sel], w.len[sel])
     if not np.array_equal(got, exp):
         raise SystemExit(f"bench output mismatch vs oracle ({int((got != exp).any(1).sum())} of {sel.size})")
+
+
+DUMP_MAX_ROWS = 1 << 18    # x 32 float32 = 32 MB, over all ranks
+DUMP_SEED = 0x4D495242
+
+
+def dump_rows(n: int, world: int = 1) -> np.ndarray:
+    """The rows of an n-digest output that --dump-outputs writes: all of them up to
+    DUMP_MAX_ROWS / N, else a sorted sample drawn from a fixed seed, the last row
+    always in it, so two builds given the same arguments write the same rows."""
+    k = max(1, DUMP_MAX_ROWS // world)
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    sel = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False)).astype(np.int64)
+    sel[-1] = n - 1
+    return sel
+
+
+def dump_outputs(dirname: str, d_out, rank: int = 0, world: int = 1) -> str:
+    """--dump-outputs: the digests the last timed step left in the caller's output
+    array, rows dump_rows(n, N), as float32 (rows, 32) byte values in DIR/digests.npy
+    (rank R of N > 1: digests_rank<R>.npy)."""
+    a = d_out.cpu().numpy() if hasattr(d_out, "cpu") else np.asarray(d_out)
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, "digests.npy" if world == 1 else f"digests_rank{rank}.npy")
+    np.save(path, a[dump_rows(a.shape[0], world)].astype(np.float32))
+    return path
 
 
 def launch_ranks(args) -> int:
@@ -463,7 +506,7 @@ def roofline(w, kern_ms: float, cfg: str, clock: dict | None = None) -> dict:
 def extra_config(eng, cfg: str, args, dev, stream, w=None) -> dict:
     """One more config timed like the headline (kernel-resident, same warmup and
     K), with its own roofline fraction and a verified sample: puts c3/c4 under
-    the driver's clock next to c2 (c3, c4 and c5's three forms in the default
+    the driver's clock next to c2 (c3, c4 and c5's three forms in a --full
     run; w: a workload already built, shared by the c5 forms)."""
     import torch
     if w is None:
@@ -623,6 +666,8 @@ def run_lib(args):
     el = time.perf_counter() - t0
     st = eng.stats()
     sh = eng.shard_stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     verify_sample(w, out)
     print(json.dumps({
         "metric": "end-to-end host API msha_digest_batch (pack + H2D + kernel + D2H), NOT the headline",
@@ -685,13 +730,16 @@ def main():
     st0 = eng.stats()
     elapsed, kern_ms, warm, warmup_ms = time_steps(step, args, dev, stream,
                                                    barrier=dist.barrier if world > 1 else None)
-    clock = clock_reading(eng)
+    clock = clock_reading(eng) if args.full else None      # a probe kernel of its own
     if world > 1:
         dist.barrier()
     eng.device_status()
     kind = kind_of(st0, eng.stats())
-    if not (args.config.startswith("u:") and w.uniform_stride != (int(w.len[0]) + 15) // 16 * 16):
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out, rank, world)
+    if args.full and not (args.config.startswith("u:") and w.uniform_stride != (int(w.len[0]) + 15) // 16 * 16):
         verify_sample(w, d_out)
+    extras = args.full and args.config == "c2" and not args.no_extra
 
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -734,7 +782,9 @@ def main():
             "library": lib_build,
             "roofline": roofline(w, kern_ms, args.config, clock),
         }
-        if world == 1 and args.config == "c2" and not args.no_extra:
+        if args.dump_outputs:
+            line["dump_outputs"] = args.dump_outputs
+        if world == 1 and extras:
             del step, d_out
             torch.cuda.empty_cache()
             line["extra_configs"] = {c: extra_config(eng, c, args, dev, stream) for c in ("c3", "c4")}
@@ -742,7 +792,7 @@ def main():
             for c in C5_FORMS:
                 line["extra_configs"][c] = extra_config(eng, c, args, dev, stream, w5)
             del w5
-    if world > 1 and args.config == "c2" and not args.no_extra:
+    if world > 1 and extras:
         # every rank takes part: c5 is quoted over the node's GPUs (BASELINE config 5)
         del step, d_out
         torch.cuda.empty_cache()
@@ -756,10 +806,10 @@ def main():
         dist.barrier()              # every rank has released its GPU
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # on the host cores, after every rank has released its GPU
             line["cpu_baseline"] = cpu_baseline(w, args.cpu_seconds)
-        if not args.no_host_api:
+        if args.full and not args.no_host_api:
             line["host_api"] = host_api_leg(args, world)
             if not args.no_host_api_unaliased:
                 line["host_api_unaliased"] = host_api_leg(args, world, unaliased=True)

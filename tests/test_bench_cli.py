@@ -1,6 +1,7 @@
 """bench.py's process contract, on CPU: --gpus N drives N rank processes (it
 starts torchrun itself when no WORLD_SIZE is set, before touching a GPU), and
-refuses a WORLD_SIZE that disagrees with --gpus."""
+refuses a WORLD_SIZE that disagrees with --gpus; --full is off by default and
+--dump-outputs writes a fixed sample. One GPU test runs a plain line end to end."""
 import os
 import subprocess
 import sys
@@ -78,6 +79,77 @@ def test_host_api_leg_failure_is_reported_not_fatal(monkeypatch):
     assert seen["cmd"][2:] == ["--mode", "lib", "--config", "c5", "--gpus", "1", "--steps", "5", "--warmup", "2"]
     assert "WORLD_SIZE" not in seen["env"] and "MASTER_PORT" not in seen["env"]
     assert seen["env"]["MSHA_VIRTUAL_SHARDS"] == "2"
+
+
+def test_full_is_off_by_default(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert not args.full and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_a_fixed_float32_sample(tmp_path):
+    """--dump-outputs: every row of a small output; of a large one the same seeded
+    rows each time (the last row among them), float32, within 64 MB over all ranks."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    small = np.arange(100 * 32, dtype=np.uint8).reshape(100, 32)
+    a = np.load(bench.dump_outputs(str(tmp_path / "s"), small))
+    assert a.dtype == np.float32 and np.array_equal(a, small)
+    n = bench.DUMP_MAX_ROWS + 4097
+    big = np.random.default_rng(1).integers(0, 256, (n, 32), dtype=np.uint8)
+    p = bench.dump_outputs(str(tmp_path / "b"), big)
+    assert os.path.basename(p) == "digests.npy"
+    b = np.load(p)
+    sel = bench.dump_rows(n)
+    assert b.dtype == np.float32 and b.shape == (bench.DUMP_MAX_ROWS, 32) and b.nbytes <= 64 << 20
+    assert np.all(np.diff(sel) > 0) and sel[0] >= 0 and sel[-1] == n - 1
+    assert np.array_equal(b, big[sel]) and np.array_equal(sel, bench.dump_rows(n))
+    assert np.array_equal(b, np.load(bench.dump_outputs(str(tmp_path / "b2"), big)))
+    # N ranks share the budget, one file each
+    p3 = bench.dump_outputs(str(tmp_path / "r"), big, rank=3, world=8)
+    assert os.path.basename(p3) == "digests_rank3.npy"
+    assert np.array_equal(np.load(p3), big[bench.dump_rows(n, 8)]) and bench.dump_rows(n, 8).size == bench.DUMP_MAX_ROWS // 8
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_digests(tmp_path):
+    """A plain run prints one line with the headline figures and ms_per_step for the
+    --steps it was given, runs none of the --full legs, and --dump-outputs writes the
+    last timed step's digests: checked against the oracle on a stride of the rows."""
+    import json
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import oracle
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--min-warmup-ms", "0", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["metric"] == bench.METRIC and d["unit"] == "digests/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "u32" and d["steps"] == 3 and d["warmup_steps_run"] == 1
+    n = d["config"]["messages_per_gpu"]
+    assert d["ms_per_step"] > 0 and abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for leg in ("extra_configs", "cpu_baseline", "host_api", "host_api_unaliased"):
+        assert leg not in d, leg
+    assert d["clock_after"] is None
+    got = np.load(out / "digests.npy")
+    sel = bench.dump_rows(n)
+    assert got.dtype == np.float32 and got.shape == (sel.size, 32)
+    w = bench.build_workload("c2", 0, 1)
+    pick = np.arange(0, sel.size, 61)
+    exp = oracle.digest_batch(w.arena, w.off[sel[pick]], w.len[sel[pick]])
+    assert np.array_equal(got[pick], exp.astype(np.float32))
 
 
 def test_c5_forms_share_the_workload_and_count_hashed_blocks():

@@ -81,7 +81,7 @@ def test_bench_two_ranks_on_the_engine():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device",
                         "--steps", "5", "--warmup", "2", "--min-warmup-ms", "50", "--cpu-seconds", "1.5",
-                        "--no-host-api-unaliased"],
+                        "--no-host-api-unaliased", "--full"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

@@ -21,6 +21,6 @@ for l in open('$OUT/slices.jsonl'):
     d = json.loads(l); print(d['world'], d['form'].ljust(11), round(d['kernel_ms'], 3), 'ms', d['kernel'])"
 fi
 if [[ ${STEPS:-all} == all || $STEPS == *bench* ]]; then
-  timeout -k 10 300 python bench.py --no-host-api --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; stop $? bench
+  timeout -k 10 300 python bench.py --full --no-host-api --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; stop $? bench
   python3 -c "import json; d=json.load(open('$OUT/bench.json')); print('c2', round(d['kernel_ms_mean']*1e3,2), 'us frac', round(d['roofline']['frac'],4), {k: (round(v['kernel_ms_mean'],4), round(v['frac'],4)) for k, v in d['extra_configs'].items()})"
 fi

@@ -5,7 +5,7 @@ set -u
 OUT=${OUT:-gpurun_out/r05_reps}
 mkdir -p $OUT
 for i in 1 2 3; do
-  timeout -k 10 400 python bench.py --no-host-api > $OUT/bench_$i.json 2> $OUT/bench_$i.err || { tail -3 $OUT/bench_$i.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --no-host-api > $OUT/bench_$i.json 2> $OUT/bench_$i.err || { tail -3 $OUT/bench_$i.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$OUT/bench_$i.json'))
 print($i, 'c2 %.4g' % d['value'], 'frac %.4f' % d['roofline']['frac'], 'clock %.3f' % d['effective_clock_ghz'],

@@ -13,7 +13,7 @@ if [[ ${STEPS:-all} == all || $STEPS == *tests* ]]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; stop $? smoke
 fi
 if [[ ${STEPS:-all} == all || $STEPS == *bench* ]]; then
-  timeout -k 10 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; stop $? bench
+  timeout -k 10 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; stop $? bench
   python3 -c "import json; d=json.load(open('$OUT/bench_default.json')); print('c2', d['value'], d['roofline']['frac'], 'clock_after', d.get('clock_after', {}).get('effective_clock_ghz'), {k: (round(v['frac'],4), v.get('kernel')) for k, v in d['extra_configs'].items()}, 'host_api', d['host_api'].get('value'), 'unaliased', d.get('host_api_unaliased', {}).get('value'))"
 fi
 if [[ ${STEPS:-all} == all || $STEPS == *prof* ]]; then

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/r06_reps/$(date +%s)
 mkdir -p $OUT
 for rep in 1 2; do
-  timeout -k 10 400 python bench.py --no-cpu-baseline --no-host-api > $OUT/bench_rep$rep.json 2> $OUT/bench_rep$rep.err \
+  timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-host-api > $OUT/bench_rep$rep.json 2> $OUT/bench_rep$rep.err \
     || { tail $OUT/bench_rep$rep.err; exit 1; }
   python3 -c "
 import json; d = json.load(open('$OUT/bench_rep$rep.json'))
