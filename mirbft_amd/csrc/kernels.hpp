@@ -121,6 +121,11 @@ struct PlanArgs {
 };
 hipError_t launch_plan(const PlanArgs& a, hipStream_t st);
 
+// The planner kernels' tiling: 256 threads, kPlanItems messages each. The host sizes
+// the per-tile scratch (apairs / acount, tkeys / tkcount, tstat) from it.
+constexpr uint32_t kPlanItems = 16;
+constexpr uint32_t kPlanTile = 256 * kPlanItems;
+
 // Device-side planning of a device-resident batch (plan.hip,
 // msha_digest_batch_device_planned): every array is device memory of one GPU.
 // Lanes = messages, or with a table only the first of each (off, len) key
@@ -148,12 +153,10 @@ struct FoldArgs {
   // rep << 32 | i for k < acount[tile] -- message i's digest is message rep's
   uint64_t* apairs = nullptr;
   uint32_t* acount = nullptr;
-  uint64_t* tmax = nullptr;   // (with table) ceil(n / 4096): largest offset before each tile
-  uint64_t* tsum = nullptr;   // (early head) 2 per tile: the tile's short messages' blocks, its longest chain
-  // Round 6: (with table, non-null) the insert finds its tile's prefix itself, by a
+  // (with table) the insert finds the largest offset before its tile itself, by a
   // decoupled look-back over ceil(n / 4096) zeroed status words (plan.hip
-  // tile_lookback) -- no k_fold_tilemax / k_fold_tilescan; then one more zeroed
-  // word: look-backs that gave up waiting (0 expected; see tile_lookback)
+  // tile_lookback); then one more zeroed word: look-backs that gave up waiting
+  // (0 expected; see tile_lookback)
   uint64_t* tstat = nullptr;
   // 2 x kGridWords zeroed words: k_fold_longs' then k_fold_longs_gate's grid reduction
   uint32_t* grid_ws = nullptr;
@@ -174,47 +177,26 @@ struct FoldArgs {
   uint32_t* info;             // [0] lanes, [1] positions the lane kernel skips (the head's),
                               // [2] distinct long payloads, [3] unused,
                               // [4] the early head's lanes (0: none), [5] the late head's,
-                              // [6] the first decision (0: no early head), by k_fold_tilescan,
-                              // or with early_fork by k_fold_longs_gate, [7..15] unused (the
-                              // list's and the gate's sums: grid_ws),
+                              // [6] the first decision (0: no early head), by
+                              // k_fold_longs_gate, [7..15] unused (the list's and the
+                              // gate's sums: grid_ws),
                               // [16] lanes of >= long_blocks blocks, [17] the scan's cut (the
-                              // scatter resolves [1] and [5] from them and [4]), [20] / [21]
-                              // (early_only) the eight- / two-lane early head's lanes
+                              // scatter resolves [1] and [5] from them and [4])
                               // (all 32 words zeroed by the caller)
-  // The early head (folding only; long_blocks 0: off): k_fold_tilescan sizes the
-  // batch (info[6]: 0 when the short messages alone outlast the longest chain);
-  // unless it stood down there, k_fold_longs claims every message of >=
-  // long_blocks blocks in the alias table beside the insert, listing each
+  // The early head (folding only; long_blocks 0: off), on a stream of its own
+  // forked right after the planner's memsets: k_fold_longs_gate, a pass over len
+  // alone, sizes the batch (info[6]: 0 when the short messages alone outlast the
+  // longest chain); unless it stood down there, k_fold_longs claims every message
+  // of >= long_blocks blocks in the alias table beside the insert, listing each
   // distinct one in longs; when there are at most long_cap, and their chain
   // outlasts the lane kernel's share, they are the head (info[4]), launched right
-  // then on the two-lane kernel over longs instead of after the scan and
-  // scatter, and k_fold_insert never takes a long message as fresh (so its
-  // representative is the listed one).
+  // then over longs instead of after the scan and scatter, and k_fold_insert never
+  // takes a long message as fresh (so its representative is the listed one).
   uint32_t* longs = nullptr;
   // off and len both 16-byte aligned: the per-thread runs of 16 messages load as
   // 16-byte vectors (plan.hip load_run)
   uint32_t vec = 0;
   uint32_t long_blocks = 0;
-  // Round 6: the early head's first decision and list run on the
-  // head's stream forked BEFORE the tile prefix (k_fold_longs_gate, a pass over len
-  // alone, then k_fold_longs), so the head's chain does not wait for the prefix;
-  // k_fold_tilemax / k_fold_tilescan then size only the offsets.
-  uint32_t early_fork = 0;
-  // Round 6: with the work-stealing lane kernel (k_digest_batch_ws) the head's cut
-  // keeps every lane of at least ws_long blocks off the lane kernel when it can
-  // (a long chain there shares a SIMD with same-age waves: kernels.hip); 0: off.
-  uint32_t ws_long = 0;
-  uint32_t longs_wgs = 0;  // k_fold_longs / k_fold_longs_gate workgroups (0: 4 a CU; A/B MSHA_LONGS_WGS)
-  uint32_t gate_wgs = 0;   // k_fold_longs_gate's workgroups (0: 64; MSHA_GATE_WGS)
-  // (early_fork, A/B MSHA_EARLY_ONLY) the early head takes every distinct long payload
-  // the list holds: info[20] arms the eight-lane launch (its chain the long pole),
-  // info[21] the two-lane one; no late head (the scatter leaves info[1] = the early
-  // head's lanes or 0)
-  uint32_t early_only = 0;
-  // Round 6: the insert's claims list the early head (every claimant of >= long_blocks
-  // blocks) and the scan decides it (info[4], [20], [21]): no k_fold_longs_gate /
-  // k_fold_longs pass beside the insert; implies early_only
-  uint32_t insert_list = 0;
   uint32_t long_cap = 0;
   uint32_t head_cap = 0;      // 0: no head
   uint32_t simds = 1024;
@@ -234,26 +216,21 @@ struct FoldArgs {
   uint32_t early_cycles = 3500;  // the same for the early head's kernel (its stand-down rule)
   uint32_t head_pct = 100;
   uint32_t head_per_wg = 128;    // messages per head workgroup (one CU each)
-  uint32_t tiebreak = 1;         // head-bound ties go to the cut with the most lane-kernel room (A/B: 0)
-  // test build only (-DMSHA_FOLD_RACE_TEST, MSHA_FOLD_LONGS_SKIP_ODD=1): k_fold_longs
-  // leaves every long payload whose table hash is odd unlisted, a state the product
-  // kernels cannot reach, to exercise the scan/scatter defensive check
+#ifdef MSHA_FOLD_RACE_TEST
+  // test build only (MSHA_FOLD_LONGS_SKIP_ODD=1): k_fold_longs leaves every long
+  // payload whose table hash is odd unlisted, a state the product kernels cannot
+  // reach, to exercise the scan/scatter defensive check
   uint32_t race_test = 0;
+#endif
 };
-// Folding only: the tile maxima and their prefix (k_fold_tilemax, k_fold_tilescan),
-// with the early head's list and decision when long_blocks is set; then
-// launch_fold_plan: the insert (or, unfolded, the counts), scan and scatter.
-hipError_t launch_fold_prefix(const FoldArgs& a, hipStream_t st);
-// The insert and the scan on st; the scatter on sst (the side stream of the late
-// head: when it is not st, st records `fork` after the scan and sst waits for it),
-// after scatter_after (may be null: the early head's list, against which the scatter
-// resolves the heads).
-// after_scan (may be null): recorded on st right after the scan (the early head's
-// stream waits for it when the insert lists the early head: FoldArgs::insert_list).
+// launch_fold_plan: the insert (or, unfolded, the counts) and the scan on st; the
+// scatter on sst (the side stream of the late head: when it is not st, st records
+// `fork` after the scan and sst waits for it), after scatter_after (may be null:
+// the early head's list, against which the scatter resolves the heads).
 hipError_t launch_fold_plan(const FoldArgs& a, hipStream_t st, hipStream_t sst, hipEvent_t fork,
-                            hipEvent_t scatter_after, hipEvent_t after_scan = nullptr);
-// The early head's list (FoldArgs::longs): on a stream of its own, after the
-// prefix, beside the alias insert (both claim through the same table).
+                            hipEvent_t scatter_after);
+// The early head's first decision and list (k_fold_longs_gate, k_fold_longs): on
+// the head's stream, beside the alias insert (both claim through the same table).
 hipError_t launch_fold_longs(const FoldArgs& a, int cus, hipStream_t st);
 // out[i] = out[rep] for every folded message (FoldArgs::apairs), after the hashing.
 hipError_t launch_fold_fill(const FoldArgs& a, uint8_t* out, hipStream_t st);

@@ -245,9 +245,9 @@ struct Device {
   // planned device calls (msha_digest_batch_device_planned): alias table,
   // representatives, bucket counters, lane order, [lanes | head]; the head of
   // long chains runs on side_stream, forked from and joined to the caller's
-  DevBuf f_table, f_rep, f_tmax, f_cnt, f_order, f_key, f_tkeys, f_longs;
+  DevBuf f_table, f_rep, f_cnt, f_order, f_key, f_tkeys, f_longs;
   hipStream_t head_stream = nullptr;  // a folded call's early head (FoldArgs::longs)
-  hipEvent_t ev_longs = nullptr, ev_join2 = nullptr, ev_hready = nullptr;
+  hipEvent_t ev_longs = nullptr, ev_join2 = nullptr;
   uint32_t f_epoch = 0;  // the alias table's epoch tag of the last folded call (plan.hip fold_claim)
   DevBuf probe;  // msha_clock_probe: stamps + sink
   // direct path heads (launch_head): their digests, lane-indexed; read back with
@@ -277,7 +277,7 @@ struct Device {
     gather_pool.reset();
     for (DevBuf* b : {&arena, &off, &len, &order, &out, &err, &idx, &begin, &table, &sm_in, &sm_out, &p_meta,
                       &p_gmap, &p_devoff, &p_table, &p_slot, &p_rep, &p_cnt, &p_small, &f_table, &f_rep,
-                      &f_tmax, &f_cnt, &f_order, &f_key, &f_tkeys, &f_longs, &probe, &p_head})
+                      &f_cnt, &f_order, &f_key, &f_tkeys, &f_longs, &probe, &p_head})
       b->release();
     if (split_flags) (void)hipFree(split_flags);
     split_flags = nullptr;
@@ -286,7 +286,7 @@ struct Device {
       b->release();
     for (hipEvent_t* e : {&ev0, &ev1, &ev_up0, &ev_up1, &ev_k0, &ev_meta, &ev_plan, &ev_p0, &ev_p1, &slot_free[0],
                           &slot_free[1], &chunk_in, &ev_fork, &ev_fplan, &ev_join, &ev_fdone, &ev_head,
-                          &ev_longs, &ev_join2, &ev_hready}) {
+                          &ev_longs, &ev_join2}) {
       if (*e) (void)hipEventDestroy(*e);
       *e = nullptr;
     }
@@ -2331,6 +2331,165 @@ void run_direct(msha_ctx* ctx, double t0, uint64_t n, const uint64_t* off, const
   call_stats(ctx, t0, t_plan);
 }
 
+// msha_digest_batch_device_planned's knobs, read once per call
+// (tests switch them within one process), and the kernel choices they decide.
+struct PlanKnobs {
+  bool all_coop;    // few messages: one cooperative launch over the planned order
+  bool head;        // otherwise: the longest chains (if any outlast the launch) on a head kernel
+  bool two_lane;    // the head on k_digest_chain2, not the cooperative kernel
+  bool eight_lane;  // the early head on k_digest_chain8
+  bool early;       // an early head (FoldArgs::longs)
+  bool ws;          // the lane kernel steals work (k_digest_batch_ws)
+  uint32_t head_pct, lane_cycles, wave_block_cycles;
+  bool poison_table, check_lookback, trace;
+};
+PlanKnobs read_plan_knobs(const msha_ctx* ctx, const Device& d, uint64_t n, bool fold) {
+  PlanKnobs k;
+  k.all_coop = msha::uses_coop(n, d.cus, ctx->kernel_policy);
+  k.head = !k.all_coop && ctx->kernel_policy != MSHA_KERNEL_LANE && env_u64("MSHA_PLAN_HEAD", 1) != 0;
+  // The head's kernel. Folded, a head is the few distinct long payloads: the
+  // two-lane chain (k_digest_chain2, 64 messages per CU, ~10 % fewer cycles a
+  // block) shortens it. Unfolded, a storm's head can be thousands of chains
+  // (19,456 over 8 GPUs): the cooperative kernel holds twice as many per CU,
+  // and the two-lane one made that case 3.0 -> 4.2 ms (profiles/r03_chain_dpp/).
+  // MSHA_HEAD_CHAIN2: 0 never, 2 always (A/B).
+  const uint64_t chain2 = env_u64("MSHA_HEAD_CHAIN2", 1);
+  k.two_lane = chain2 == 2 || (chain2 == 1 && fold);
+  // The EARLY head runs on the eight-lane kernel (k_digest_chain8: ~9 % fewer
+  // cycles a round, 24 messages a CU instead of 64). It exists only when its
+  // chain outlasts the lane kernel's share, so its latency is the call's; the
+  // late head (after the scan's cut, when the early head stood down: the lane
+  // kernel is the long pole) keeps the denser two-lane kernel -- on it the
+  // eight-lane one took 5 CUs' worth of the lane kernel's SIMDs for c5's 100
+  // payloads, one GPU 2.73 -> 2.84 ms (profiles/r05_chain8/).
+  // MSHA_HEAD_CHAIN8=0: the early head on the two-lane kernel too (A/B).
+  k.eight_lane = k.two_lane && env_u64("MSHA_HEAD_CHAIN8", 1) != 0;
+  // The early head (folded calls with a two-lane head): unless its gate stands it
+  // down (the short messages alone outlast the longest chain), the distinct
+  // payloads of >= kLongBlocks blocks are listed (k_fold_longs, beside the alias
+  // insert) and, when at most an eighth of the CUs' worth, start on a stream of
+  // their own right then, while the insert, the scan and the scatter still run --
+  // a folded storm's head does not wait for the whole plan. MSHA_EARLY_HEAD=0:
+  // the head after the scan's cut (A/B).
+  k.early = fold && k.head && k.two_lane && env_u64("MSHA_EARLY_HEAD", 1) != 0;
+  // The lane kernel of a folded call steals work (k_digest_batch_ws: folded c5
+  // 2.79 -> 2.69 ms, profiles/r06_ws/); an unfolded one keeps the statically
+  // mapped kernel, whose oldest-first issue runs a storm's thousands of long
+  // chains one after another (work stealing: 13.3 -> 17.6 ms). MSHA_LANE_WS:
+  // 0 never, 2 always (A/B).
+  const uint64_t lane_ws = env_u64("MSHA_LANE_WS", 1);
+  k.ws = !k.all_coop && (lane_ws == 2 || (lane_ws == 1 && fold));
+  const msha::FoldArgs dflt{};
+  k.head_pct = (uint32_t)env_u64("MSHA_PLAN_HEAD_PCT", dflt.head_pct);
+  k.lane_cycles = (uint32_t)env_u64("MSHA_PLAN_LANE_CYCLES", dflt.lane_cycles);  // A/B of the cost model
+  k.wave_block_cycles = (uint32_t)env_u64("MSHA_PLAN_WAVE_CYCLES", dflt.wave_block_cycles);
+  // MSHA_POISON_FOLD_TABLE=1 (tests): a fresh alias table is filled with words
+  // tagged with the coming epoch, as recycled memory may be -- a table that
+  // was not cleared then claims garbage indices (tests/test_gpu_planned.py)
+  k.poison_table = env_u64("MSHA_POISON_FOLD_TABLE", 0) != 0;
+  k.check_lookback = env_u64("MSHA_CHECK_LOOKBACK", 0) != 0;  // tests: no look-back gave up
+  k.trace = trace_on() || env_u64("MSHA_TRACE_PLAN", 0) != 0;
+  return k;
+}
+
+// A planned call's scratch and streams: sized, the zeroed part cleared on st (after
+// the previous planned call, whose kernels still read it), and described in the
+// FoldArgs its planner kernels take.
+msha::FoldArgs prepare_plan(Device& d, const PlanKnobs& k, const uint64_t* d_off, const uint64_t* d_len,
+                            uint64_t n, bool fold, hipStream_t st) {
+  const uint64_t ptiles = (n + msha::kPlanTile - 1) / msha::kPlanTile;
+  uint64_t cap = 1024;
+  while (cap < 2 * n) cap <<= 1;
+  // one zeroed block: info (32 words, 128 bytes), the bucket counters, FoldArgs::big,
+  // the work-stealing lane kernel's tile counters, the grid reductions' words and
+  // (folded) the look-back's status words and give-up count -- cleared by ONE
+  // memset per call
+  constexpr uint64_t zero_fixed = 128 + 4 * msha::kFoldBuckets + 16 * msha::kFoldBigBuckets +
+                                  4 * msha::kWsSlots * msha::kWsStride + 4 * 2 * msha::kGridWords;
+  static_assert(zero_fixed % 8 == 0, "the look-back's status words follow 8-byte aligned");
+  // (a multiple of 64 bytes: an unaligned tail made hipMemsetAsync a second fill kernel)
+  const uint64_t zero_bytes = (zero_fixed + (fold ? 8 * (ptiles + 1) : 0) + 63) / 64 * 64;
+  d.f_cnt.ensure(zero_bytes);
+  d.f_key.ensure(2 * n);
+  d.f_tkeys.ensure(8 * n + 4 * ptiles + 8 * msha::kPlanTile);  // per-tile key lists, then their counts
+  d.f_order.ensure(4 * n);
+  bool clear_table = false;
+  if (fold) {
+    // epoch-tagged slots (plan.hip fold_claim): cleared only when the table
+    // is (re)allocated -- hipMalloc does not zero -- or the epoch wraps. A
+    // reallocation is told by the capacity, not the pointer: hipFree then
+    // hipMalloc can hand back the same address, and the grown tail would then
+    // hold recycled words whose high half may equal the current epoch.
+    const uint64_t cap_before = d.f_table.cap;
+    d.f_table.ensure(8 * cap);
+    const bool grown = d.f_table.cap != cap_before;
+    if (grown && k.poison_table)
+      HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d.f_table.p, d.f_epoch + 1, d.f_table.cap / 4, st));
+    if (grown || d.f_epoch == 0xFFFFFFFFu) {
+      clear_table = true;
+      d.f_epoch = 0;
+    }
+    ++d.f_epoch;
+    d.f_rep.ensure(8 * n + 4 * ptiles);  // alias pairs, then their count per tile
+  }
+  // The planner's scratch (table, order, counters) is the context's: a call
+  // on another stream must not overwrite it while an earlier call still reads it.
+  if (!d.ev_fdone) HIPCHK(hipEventCreateWithFlags(&d.ev_fdone, hipEventDisableTiming));
+  if (d.fdone_recorded) HIPCHK(hipStreamWaitEvent(st, d.ev_fdone, 0));
+  if (k.head) {
+    if (!d.side_stream) HIPCHK(hipStreamCreateWithFlags(&d.side_stream, hipStreamNonBlocking));
+    for (hipEvent_t* e : {&d.ev_fork, &d.ev_fplan, &d.ev_join})
+      if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  }
+  if (clear_table) HIPCHK(hipMemsetAsync(d.f_table.p, 0, d.f_table.cap, st));
+  HIPCHK(hipMemsetAsync(d.f_cnt.p, 0, zero_bytes, st));
+  // (the order's positions past the last lane are filled by k_fold_scatter)
+  msha::FoldArgs fa;
+  fa.off = d_off;
+  fa.len = d_len;
+  fa.n = n;
+  fa.vec = ((reinterpret_cast<uintptr_t>(d_off) | reinterpret_cast<uintptr_t>(d_len)) & 15) == 0;
+  fa.tmask = cap - 1;
+  fa.epoch = d.f_epoch;
+  if (fold) {
+    fa.table = d.f_table.as<uint64_t>();
+    fa.apairs = d.f_rep.as<uint64_t>();
+    fa.acount = reinterpret_cast<uint32_t*>(fa.apairs + n);
+    fa.tstat = reinterpret_cast<uint64_t*>(d.f_cnt.as<uint8_t>() + zero_fixed);
+  }
+  fa.info = d.f_cnt.as<uint32_t>();
+  fa.cnt = fa.info + 32;
+  fa.key16 = d.f_key.as<uint16_t>();
+  fa.tkeys = d.f_tkeys.as<uint64_t>();
+  fa.tkcount = reinterpret_cast<uint32_t*>(fa.tkeys + ptiles * msha::kPlanTile);
+  fa.big = reinterpret_cast<uint64_t*>(fa.cnt + msha::kFoldBuckets);  // kFoldBuckets is even: 8-byte aligned
+  fa.order = d.f_order.as<uint32_t>();
+  fa.grid_ws = reinterpret_cast<uint32_t*>(fa.big + 2 * msha::kFoldBigBuckets) + msha::kWsSlots * msha::kWsStride;
+  fa.simds = (uint32_t)d.cus * 4;
+  fa.head_per_wg = k.two_lane ? msha::kChain2MsgsPerWg : msha::kCoopMsgsPerWg;
+  fa.head_cap = k.head ? (uint32_t)std::min<uint64_t>(n, (uint64_t)d.cus * fa.head_per_wg) : 0;
+  // cycles a chain block: two-lane head 1,427 blocks in 2.04 ms at ~2.4 GHz (r04);
+  // eight-lane (the early head): tools/chain2_anatomy 1427 8, profiles/r05_chain8/
+  fa.coop_cycles = k.two_lane ? 3500 : 4200;
+  fa.early_cycles = k.eight_lane ? 3250 : 3500;  // eight-lane: 1,427 blocks in 1.93 ms at ~2.4 GHz (r05)
+  fa.head_pct = k.head_pct;
+  fa.lane_cycles = k.lane_cycles;
+  fa.wave_block_cycles = k.wave_block_cycles;
+#ifdef MSHA_FOLD_RACE_TEST
+  fa.race_test = (uint32_t)env_u64("MSHA_FOLD_LONGS_SKIP_ODD", 0);
+#endif
+  if (k.early) {
+    fa.long_blocks = (uint32_t)kLongBlocks;
+    fa.long_cap = (uint32_t)(d.cus * (k.eight_lane ? msha::kChain8MsgsPerWg : msha::kChain2MsgsPerWg) / 8);
+    d.f_longs.ensure(4 * (uint64_t)fa.long_cap);
+    fa.longs = d.f_longs.as<uint32_t>();
+    if (!d.head_stream) HIPCHK(hipStreamCreateWithFlags(&d.head_stream, hipStreamNonBlocking));
+    for (hipEvent_t* e : {&d.ev_longs, &d.ev_join2})
+      if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  }
+  return fa;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2843,281 +3002,86 @@ int msha_digest_batch_device_planned(msha_ctx* ctx, const uint8_t* d_arena, cons
                      "msha_digest_batch_device_planned cannot be captured into a HIP graph; "
                      "use msha_digest_batch_device there");
     const bool fold = flags & MSHA_PLAN_FOLD_ALIASES;
-    // Few messages: one cooperative launch over the planned order (every
-    // workgroup gets a CU); otherwise the lane kernel, its longest chains
-    // (if any outlast the launch) on the cooperative kernel beside it.
-    const bool all_coop = msha::uses_coop(n, d.cus, ctx->kernel_policy);
-    const bool head = !all_coop && ctx->kernel_policy != MSHA_KERNEL_LANE && env_u64("MSHA_PLAN_HEAD", 1) != 0;
-    uint64_t cap = 1024;
-    while (cap < 2 * n) cap <<= 1;
-    // one zeroed block: info (32 words, 128 bytes), the bucket counters,
-    // then FoldArgs::big -- cleared by ONE memset per call
-    // (+ the work-stealing lane kernel's tile counters)
-    const uint64_t fold_zero_fixed = 128 + 4 * msha::kFoldBuckets + 16 * msha::kFoldBigBuckets +
-                                     4 * msha::kWsSlots * msha::kWsStride + 4 * 2 * msha::kGridWords;
-    // Round 6: a folded call's insert finds its tile prefix by look-back (plan.hip
-    // tile_lookback) over status words zeroed with the rest -- no k_fold_tilemax /
-    // k_fold_tilescan and their two dependent launches. MSHA_FOLD_LOOKBACK=0: the
-    // two-kernel prefix (A/B).
-    const bool lookback = fold && env_u64("MSHA_FOLD_LOOKBACK", 1) != 0;
-    const uint64_t ptiles = (n + 4095) / 4096;
-    static_assert((128 + 4 * msha::kFoldBuckets + 16 * msha::kFoldBigBuckets + 4 * msha::kWsSlots * msha::kWsStride +
-                   4 * 2 * msha::kGridWords) % 8 == 0,
-                  "the look-back's status words follow 8-byte aligned");
-    // (a multiple of 64 bytes: an unaligned tail made hipMemsetAsync a second fill kernel)
-    const uint64_t fold_zero = (fold_zero_fixed + (lookback ? 8 * (ptiles + 1) : 0) + 63) / 64 * 64;
-    d.f_cnt.ensure(fold_zero);
-    d.f_key.ensure(2 * n);
-    d.f_tkeys.ensure(8 * n + 4 * ((n + 4095) / 4096) + 8 * 4096);  // per-tile key lists, then their counts
-    d.f_order.ensure(4 * n);
-    bool clear_table = false;
-    if (fold) {
-      // epoch-tagged slots (plan.hip fold_claim): cleared only when the table
-      // is (re)allocated -- hipMalloc does not zero -- or the epoch wraps. A
-      // reallocation is told by the capacity, not the pointer: hipFree then
-      // hipMalloc can hand back the same address, and the grown tail would then
-      // hold recycled words whose high half may equal the current epoch.
-      const uint64_t cap_before = d.f_table.cap;
-      d.f_table.ensure(8 * cap);
-      const bool grown = d.f_table.cap != cap_before;
-      // MSHA_POISON_FOLD_TABLE=1 (tests): a fresh allocation is filled with words
-      // tagged with the coming epoch, as recycled memory may be -- a table that
-      // was not cleared then claims garbage indices (tests/test_gpu_planned.py)
-      if (grown && env_u64("MSHA_POISON_FOLD_TABLE", 0))
-        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d.f_table.p, d.f_epoch + 1, d.f_table.cap / 4, st));
-      if (grown || d.f_epoch == 0xFFFFFFFFu) {
-        clear_table = true;
-        d.f_epoch = 0;
-      }
-      ++d.f_epoch;
-      d.f_rep.ensure(8 * n + 4 * ((n + 4095) / 4096));  // alias pairs, then their count per tile
-      d.f_tmax.ensure(8 * 3 * ((n + 4095) / 4096));  // tile maxima, then 2 x tsum per tile
-    }
-    // The planner's scratch (table, order, counters) is the context's: a call
-    // on another stream must not overwrite it while an earlier call still reads it.
-    if (!d.ev_fdone) HIPCHK(hipEventCreateWithFlags(&d.ev_fdone, hipEventDisableTiming));
-    if (d.fdone_recorded) HIPCHK(hipStreamWaitEvent(st, d.ev_fdone, 0));
-    // With a head, the planner and then the head's cooperative launch run on
-    // the side stream, and the lane kernel on `stream` waits for the planner's
-    // event: the head's packet follows the planner in its own queue while the
-    // lane kernel's needs a cross-queue signal, so the head's workgroups are
-    // resident before the lane kernel fills every SIMD (queued the other way
-    // round, the head could not get a CU's registers until the lane kernel
-    // drained: c5 folded 6.2 ms, its 1,427-block chain starting at the end).
-    // Round 6: the memsets, the insert and the scan run on the caller's stream, and
-    // the side stream joins at the scatter (with the early head's list), so a step
-    // starts without a cross-queue hand-off (~20 us of a folded c5 step's timeline,
-    // profiles/r06_plan7/).
-    hipStream_t ps = st;  // the scatter's and the late head's
-    if (head) {
-      if (!d.side_stream) HIPCHK(hipStreamCreateWithFlags(&d.side_stream, hipStreamNonBlocking));
-      for (hipEvent_t* e : {&d.ev_fork, &d.ev_fplan, &d.ev_join})
-        if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-      ps = d.side_stream;
-    }
-    if (clear_table) HIPCHK(hipMemsetAsync(d.f_table.p, 0, d.f_table.cap, st));
-    HIPCHK(hipMemsetAsync(d.f_cnt.p, 0, fold_zero, st));
-    // (the order's positions past the last lane are filled by k_fold_scatter)
-    msha::FoldArgs fa;
-    fa.off = d_off;
-    fa.len = d_len;
-    fa.n = n;
-    fa.vec = ((reinterpret_cast<uintptr_t>(d_off) | reinterpret_cast<uintptr_t>(d_len)) & 15) == 0;
-    fa.table = fold ? d.f_table.as<uint64_t>() : nullptr;
-    fa.tmask = cap - 1;
-    fa.epoch = d.f_epoch;
-    fa.apairs = fold ? d.f_rep.as<uint64_t>() : nullptr;
-    fa.acount = fold ? reinterpret_cast<uint32_t*>(fa.apairs + n) : nullptr;
-    fa.tmax = fold ? d.f_tmax.as<uint64_t>() : nullptr;
-    fa.tsum = fold ? fa.tmax + (n + 4095) / 4096 : nullptr;
-    fa.info = d.f_cnt.as<uint32_t>();
-    fa.cnt = fa.info + 32;
-    fa.key16 = d.f_key.as<uint16_t>();
-    fa.tkeys = d.f_tkeys.as<uint64_t>();
-    fa.tkcount = reinterpret_cast<uint32_t*>(fa.tkeys + (n + 4095) / 4096 * 4096);
-    fa.big = reinterpret_cast<uint64_t*>(fa.cnt + msha::kFoldBuckets);  // kFoldBuckets is even: 8-byte aligned
-    fa.order = d.f_order.as<uint32_t>();
-    fa.tstat = lookback ? reinterpret_cast<uint64_t*>(d.f_cnt.as<uint8_t>() + fold_zero_fixed) : nullptr;
-    fa.grid_ws = reinterpret_cast<uint32_t*>(fa.big + 2 * msha::kFoldBigBuckets) + msha::kWsSlots * msha::kWsStride;
-    fa.simds = (uint32_t)d.cus * 4;
-    // The head's kernel. Folded, a head is the few distinct long payloads: the
-    // two-lane chain (k_digest_chain2, 64 messages per CU, ~10 % fewer cycles a
-    // block) shortens it. Unfolded, a storm's head can be thousands of chains
-    // (19,456 over 8 GPUs): the cooperative kernel holds twice as many per CU,
-    // and the two-lane one made that case 3.0 -> 4.2 ms (profiles/r03_chain_dpp/).
-    // MSHA_HEAD_CHAIN2: 0 never, 2 always (A/B).
-    const uint64_t chain2_env = env_u64("MSHA_HEAD_CHAIN2", 1);
-    const bool two_lane = chain2_env == 2 || (chain2_env == 1 && fold);
-    // Round 5: the EARLY head runs on the eight-lane kernel (k_digest_chain8:
-    // ~9 % fewer cycles a round, 24 messages a CU instead of 64). It exists only
-    // when its chain outlasts the lane kernel's share, so its latency is the
-    // call's; the late head (after the scan's cut, when the early head stood
-    // down: the lane kernel is the long pole) keeps the denser two-lane kernel --
-    // on it the eight-lane one took 5 CUs' worth of the lane kernel's SIMDs for
-    // c5's 100 payloads, one GPU 2.73 -> 2.84 ms (profiles/r05_chain8/).
-    // MSHA_HEAD_CHAIN8=0: the early head on the two-lane kernel too (A/B).
-    const bool eight_lane = two_lane && env_u64("MSHA_HEAD_CHAIN8", 1) != 0;
-    fa.head_per_wg = two_lane ? msha::kChain2MsgsPerWg : msha::kCoopMsgsPerWg;
-    fa.head_cap = head ? (uint32_t)std::min<uint64_t>(n, (uint64_t)d.cus * fa.head_per_wg) : 0;
-    // cycles a chain block: two-lane head 1,427 blocks in 2.04 ms at ~2.4 GHz (r04);
-    // eight-lane (the early head): tools/chain2_anatomy 1427 8, profiles/r05_chain8/
-    fa.coop_cycles = two_lane ? 3500 : 4200;
-    fa.early_cycles = eight_lane ? 3250 : 3500;  // eight-lane: 1,427 blocks in 1.93 ms at ~2.4 GHz (r05)
-    fa.tiebreak = (uint32_t)env_u64("MSHA_PLAN_TIEBREAK", 1);
-    fa.race_test = (uint32_t)env_u64("MSHA_FOLD_LONGS_SKIP_ODD", 0);
-    // The lane kernel of a folded call steals work (k_digest_batch_ws: folded c5
-    // 2.79 -> 2.69 ms, profiles/r06_ws/); an unfolded one keeps the statically
-    // mapped kernel, whose oldest-first issue runs a storm's thousands of long
-    // chains one after another (work stealing: 13.3 -> 17.6 ms). MSHA_LANE_WS:
-    // 0 never, 2 always (A/B).
-    const uint64_t lane_ws = env_u64("MSHA_LANE_WS", 1);
-    const bool ws = !all_coop && (lane_ws == 2 || (lane_ws == 1 && fold));
-    // MSHA_WS_LONG=k (A/B): the cut also keeps chains of >= k blocks off it. Every
-    // k tried lost to the cost model alone, which takes fewer head CUs (folded c5,
-    // 3 reps: 2.661-2.669 ms; k = 600 / 256 / 64: 2.715-2.719 / 2.709-2.744 /
-    // 2.725-2.736; static lane kernel 2.78-2.89; profiles/r06_ws2/)
-    const uint64_t ws_long_env = env_u64("MSHA_WS_LONG", 0);
-    fa.ws_long = ws ? (ws_long_env ? (uint32_t)std::min<uint64_t>(ws_long_env, 0xFFFFFFFFull) : 0xFFFFFFFFu) : 0u;
-    fa.head_pct = (uint32_t)env_u64("MSHA_PLAN_HEAD_PCT", 100);
-    fa.lane_cycles = (uint32_t)env_u64("MSHA_PLAN_LANE_CYCLES", fa.lane_cycles);  // A/B of the cost model
-    fa.wave_block_cycles = (uint32_t)env_u64("MSHA_PLAN_WAVE_CYCLES", fa.wave_block_cycles);
-    // The early head (folded calls with a two-lane head): unless the tile prefix
-    // already stood it down (the short messages alone outlast the longest chain),
-    // the distinct payloads of >= kLongBlocks blocks are listed (k_fold_longs,
-    // beside the alias insert) and, when at most an eighth of the CUs' worth,
-    // start on the two-lane kernel on a stream of their own right then, while
-    // the insert, the scan and the scatter still run -- a folded storm's head
-    // does not wait for the whole plan. MSHA_EARLY_HEAD=0: the head after the
-    // scan's cut (A/B).
-    const bool early = fold && head && two_lane && env_u64("MSHA_EARLY_HEAD", 1) != 0;
-    if (early) {
-      fa.long_blocks = (uint32_t)kLongBlocks;
-      fa.long_cap = (uint32_t)(d.cus * (eight_lane ? msha::kChain8MsgsPerWg : msha::kChain2MsgsPerWg) / 8);
-      d.f_longs.ensure(4 * (uint64_t)fa.long_cap);
-      fa.longs = d.f_longs.as<uint32_t>();
-      if (!d.head_stream) HIPCHK(hipStreamCreateWithFlags(&d.head_stream, hipStreamNonBlocking));
-      for (hipEvent_t* e : {&d.ev_longs, &d.ev_join2})
-        if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    }
-    // Round 6 A/B (MSHA_EARLY_FORK=1): the head's stream forks before the tile
-    // prefix, right after the memsets, and makes its first decision itself
-    // (k_fold_longs_gate over len). The chain then starts ~13 us sooner over 8
-    // GPUs with no measurable step change, and one GPU lost ~27 us (the gate's
-    // pass beside the prefix): off by default (profiles/r06_call4/).
-    // With the look-back there is no tile prefix to decide in: the gate always
-    // decides (64 workgroups; MSHA_GATE_WGS).
-    // Round 6 (MSHA_INSERT_LIST): with the look-back, the insert's own claims list
-    // the early head and the scan decides it -- no gate or list pass beside the
-    // insert -- and no late head runs (FoldArgs::insert_list).
-    const bool insert_list = early && lookback && env_u64("MSHA_INSERT_LIST", 0) != 0;
-    fa.insert_list = insert_list;
-    fa.early_fork = early && !insert_list && (lookback || env_u64("MSHA_EARLY_FORK", 0) != 0);
-    fa.longs_wgs = (uint32_t)env_u64("MSHA_LONGS_WGS", 0);
-    fa.gate_wgs = (uint32_t)env_u64("MSHA_GATE_WGS", 0);
-    // Round 6 A/B (MSHA_EARLY_ONLY=1): the early head takes every distinct long
-    // payload whether or not its chain is the call's long pole -- on the eight-lane
-    // kernel when it is, the two-lane one when the lane kernel is (both launched, the
-    // list's last workgroup arms one) -- and no late head is launched: the scatter
-    // and the lane kernel follow on the caller's stream, without the side stream's
-    // two cross-queue hand-offs. Payloads the list cannot hold stay lanes.
-    const bool early_only = insert_list || (fa.early_fork && env_u64("MSHA_EARLY_ONLY", 0) != 0);
-    fa.early_only = early_only;
-    const bool late_head = head && !early_only;
-    if (fa.early_fork) {
+    const PlanKnobs k = read_plan_knobs(ctx, d, n, fold);
+    // Three streams. The memsets, the insert (or the counts), the scan, the lane
+    // kernel and the fill run on the caller's stream, so a step starts without a
+    // cross-queue hand-off (~20 us of a folded c5 step's timeline, profiles/r06_plan7/).
+    // The early head's gate, list and chain run on head_stream, forked right after
+    // the memsets (DESIGN.md §(d) "Head before the tile prefix"). The scatter and
+    // the late head run on side_stream, forked after the scan: the head's packet
+    // follows the scatter in its own queue while the lane kernel's needs a
+    // cross-queue signal, so the head's workgroups are resident before the lane
+    // kernel fills every SIMD (queued the other way round, the head could not get
+    // a CU's registers until the lane kernel drained: c5 folded 6.2 ms, its
+    // 1,427-block chain starting at the end). The variants that moved the list into
+    // the insert or dropped the late head lost: DESIGN.md §(d) "The folded planner".
+    // 1. the memsets
+    const msha::FoldArgs fa = prepare_plan(d, k, d_off, d_len, n, fold, st);
+    if (k.early) {
+      // 2. the head stream's fork
       HIPCHK(hipEventRecord(d.ev_longs, st));
       HIPCHK(hipStreamWaitEvent(d.head_stream, d.ev_longs, 0));
-    }
-    HIPCHK(msha::launch_fold_prefix(fa, st));
-    // the early head's launches on its stream: after the list (k_fold_longs) or,
-    // listed by the insert, after the scan (its event recorded by launch_fold_plan,
-    // so these are queued after that call)
-    auto launch_early_head = [&]() {
+      // 3. the gate and the list, beside the alias insert
+      HIPCHK(msha::launch_fold_longs(fa, d.cus, d.head_stream));
+      HIPCHK(hipEventRecord(d.ev_longs, d.head_stream));
+      // 4. the early head: the listed payloads (info[4] of them; 0: it stood down)
       msha::LaneGate eg;
-      eg.head = early_only && eight_lane ? fa.info + 20 : fa.info + 4;
+      eg.head = fa.info + 4;
       eg.head_part = true;
       eg.two_lane = true;
-      eg.eight_lane = eight_lane;
+      eg.eight_lane = k.eight_lane;
       msha::LaunchKind ek;
       HIPCHK(msha::launch_digest_batch(d_arena, d_off, d_len, fa.longs, nullptr, fa.long_cap, d_out,
                                        d.err.as<uint32_t>(), d.cus, MSHA_KERNEL_COOP, d.head_stream, nullptr,
                                        &ek, &eg));
       count_launch(ctx, nullptr, ek);
-      if (early_only && eight_lane) {  // the same list on the two-lane kernel when not the long pole
-        eg.head = fa.info + 21;
-        eg.eight_lane = false;
-        HIPCHK(msha::launch_digest_batch(d_arena, d_off, d_len, fa.longs, nullptr, fa.long_cap, d_out,
-                                         d.err.as<uint32_t>(), d.cus, MSHA_KERNEL_COOP, d.head_stream, nullptr,
-                                         &ek, &eg));
-        count_launch(ctx, nullptr, ek);
-      }
       HIPCHK(hipEventRecord(d.ev_join2, d.head_stream));
-    };
-    if (early && !insert_list) {
-      // the list runs beside the tile prefix (forked) or after it, and beside the
-      // alias insert
-      if (!fa.early_fork) {
-        HIPCHK(hipEventRecord(d.ev_longs, st));
-        HIPCHK(hipStreamWaitEvent(d.head_stream, d.ev_longs, 0));
-      }
-      HIPCHK(msha::launch_fold_longs(fa, d.cus, d.head_stream));
-      HIPCHK(hipEventRecord(d.ev_longs, d.head_stream));
-      launch_early_head();
     }
-    HIPCHK(msha::launch_fold_plan(fa, st, late_head ? ps : st, d.ev_fork,
-                                  early && !insert_list ? d.ev_longs : nullptr,
-                                  insert_list ? d.ev_longs : nullptr));
-    if (insert_list) {  // (ev_longs here: after the scan, on st)
-      HIPCHK(hipStreamWaitEvent(d.head_stream, d.ev_longs, 0));
-      // the lane kernel waits until the head's stream reaches its launches (an event
-      // recorded just before them): dispatched together, the lane kernel ran ~25 %
-      // more cycles a block (profiles/r06_il_stamps/); the wait overlaps the scatter
-      if (env_u64("MSHA_INSERT_LIST_SYNC", 1)) {
-        if (!d.ev_hready) HIPCHK(hipEventCreateWithFlags(&d.ev_hready, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(d.ev_hready, d.head_stream));
-      }
-      launch_early_head();
-    }
-    const uint32_t* order = d.f_order.as<uint32_t>();
+    // 5. the insert and the scan, then the scatter (with a head on the side stream,
+    // and after the list, against which it resolves the heads)
+    HIPCHK(msha::launch_fold_plan(fa, st, k.head ? d.side_stream : st, d.ev_fork, k.early ? d.ev_longs : nullptr));
     msha::LaunchKind kind;
-    if (all_coop) {
-      HIPCHK(msha::launch_digest_batch(d_arena, d_off, d_len, order, nullptr, n, d_out, d.err.as<uint32_t>(),
+    if (k.all_coop) {
+      HIPCHK(msha::launch_digest_batch(d_arena, d_off, d_len, fa.order, nullptr, n, d_out, d.err.as<uint32_t>(),
                                        d.cus, MSHA_KERNEL_COOP, st, nullptr, &kind));
       count_launch(ctx, nullptr, kind);
     } else {
-      msha::LaneGate body;
-      body.head = fa.info + 1;
-      // Round 6: the body on the work-stealing lane kernel (kernels.hip
-      // k_digest_batch_ws), over the planned lanes only (fa.ws_long, set before
-      // the plan: the cut then keeps long chains off it)
-      if (fa.ws_long) {
-        body.ws_ctr = reinterpret_cast<uint32_t*>(fa.big + 2 * msha::kFoldBigBuckets);
-        body.lanes = fa.info;
-      }
-      if (late_head) {
+      if (k.head) {
+        // 6. the late head: the scan's cut (info[5]; 0 when the early head has the long lanes)
         HIPCHK(hipEventRecord(d.ev_fplan, d.side_stream));
         msha::LaneGate hg;
-        hg.head = fa.info + 5;  // the scan's cut (0 when the early head has the long lanes)
+        hg.head = fa.info + 5;
         hg.head_part = true;
-        hg.two_lane = two_lane;
-        HIPCHK(msha::launch_digest_batch(d_arena, d_off, d_len, order, nullptr, fa.head_cap, d_out,
+        hg.two_lane = k.two_lane;
+        HIPCHK(msha::launch_digest_batch(d_arena, d_off, d_len, fa.order, nullptr, fa.head_cap, d_out,
                                          d.err.as<uint32_t>(), d.cus, MSHA_KERNEL_COOP, d.side_stream, nullptr,
                                          &kind, &hg));
         count_launch(ctx, nullptr, kind);
         HIPCHK(hipEventRecord(d.ev_join, d.side_stream));
         HIPCHK(hipStreamWaitEvent(st, d.ev_fplan, 0));
       }
-      if (insert_list && env_u64("MSHA_INSERT_LIST_SYNC", 1)) HIPCHK(hipStreamWaitEvent(st, d.ev_hready, 0));
-      HIPCHK(msha::launch_digest_batch(d_arena, d_off, d_len, order, nullptr, n, d_out, d.err.as<uint32_t>(),
+      // 7. the lane kernel, over every lane the heads leave (info[1] skipped); the
+      // work-stealing one visits the planned lanes only (info[0])
+      msha::LaneGate body;
+      body.head = fa.info + 1;
+      if (k.ws) {
+        body.ws_ctr = reinterpret_cast<uint32_t*>(fa.big + 2 * msha::kFoldBigBuckets);
+        body.lanes = fa.info;
+      }
+      HIPCHK(msha::launch_digest_batch(d_arena, d_off, d_len, fa.order, nullptr, n, d_out, d.err.as<uint32_t>(),
                                        d.cus, ctx->kernel_policy, st, nullptr, &kind, &body));
       count_launch(ctx, nullptr, kind);
-      if (late_head) HIPCHK(hipStreamWaitEvent(st, d.ev_join, 0));
-      if (early) HIPCHK(hipStreamWaitEvent(st, d.ev_join2, 0));
+      // 8. the joins
+      if (k.head) HIPCHK(hipStreamWaitEvent(st, d.ev_join, 0));
+      if (k.early) HIPCHK(hipStreamWaitEvent(st, d.ev_join2, 0));
     }
+    // 9. the fill: every folded message copies its representative's digest
     if (fold) HIPCHK(msha::launch_fold_fill(fa, d_out, st));
-    if (lookback && env_u64("MSHA_CHECK_LOOKBACK", 0)) {  // tests: no look-back gave up (waits for the call)
+    if (fold && k.check_lookback) {  // (waits for the call)
       uint64_t gave_up = 0;
       HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(hipMemcpy(&gave_up, fa.tstat + ptiles, sizeof gave_up, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&gave_up, fa.tstat + (n + msha::kPlanTile - 1) / msha::kPlanTile, sizeof gave_up,
+                       hipMemcpyDeviceToHost));
       if (gave_up)
         throw MshaError(MSHA_ERR_HIP, "planner tile look-back gave up waiting " + std::to_string(gave_up) +
                                           " time(s) (digests exact, folding reduced)");
@@ -3125,7 +3089,7 @@ int msha_digest_batch_device_planned(msha_ctx* ctx, const uint8_t* d_arena, cons
     HIPCHK(hipEventRecord(d.ev_fdone, st));
     d.fdone_recorded = true;
     ctx->stats.planned_device_calls++;
-    if (trace_on() || env_u64("MSHA_TRACE_PLAN", 0)) {  // MSHA_TRACE: the GPU's plan (waits for the call)
+    if (k.trace) {  // MSHA_TRACE / MSHA_TRACE_PLAN: the GPU's plan (waits for the call)
       uint32_t info[2] = {0, 0};
       HIPCHK(hipStreamSynchronize(st));
       HIPCHK(hipMemcpy(info, fa.info, sizeof info, hipMemcpyDeviceToHost));

@@ -122,8 +122,7 @@ __global__ __launch_bounds__(256) void k_plan_remap(PlanArgs a) {
 // so each costs one global atomic per tile instead of one per message or per
 // wave (wave-aggregated global atomics made these two kernels 3.5 ms of c5's
 // 4 ms plan: ~2K waves of a piece queued on one hot counter).
-constexpr uint32_t kPlanItems = 16;                  // messages per thread
-constexpr uint32_t kPlanTile = 256 * kPlanItems;     // messages per workgroup
+// (kPlanItems messages per thread, kPlanTile per workgroup: kernels.hpp)
 constexpr uint32_t kPlanSlots = 1024;                // LDS key table (power of two)
 constexpr uint32_t kEmptyKey = 0xFFFFFFFFu;
 
@@ -318,8 +317,8 @@ hipError_t launch_plan(const PlanArgs& a, hipStream_t st) {
 // the hash launches read them (kernels.hpp LaneGate), so the whole call is
 // enqueued at once.
 //
-//   k_fold_tilemax, k_fold_tilescan, k_fold_insert   (folding only) messages
-//                   that may repeat an earlier payload claim (off, len) in an
+//   k_fold_insert   (folding only) messages that may repeat an earlier payload
+//                   (found by the tile look-back below) claim (off, len) in an
 //                   open-addressing table; the claimer is the key's lane (any one
 //                   will do: the digest is the same), rep[i] = that lane; and the
 //                   lanes counted per descending block-count bucket
@@ -355,8 +354,8 @@ __device__ __forceinline__ uint32_t fold_key(uint64_t len) {  // descending clas
 // EpochChange re-hashes: 5 %) probe and claim. A key first named by a
 // non-candidate and then by candidates is hashed twice -- once for the
 // non-candidate, once for the candidates' claimant -- with the same digest.
-// Tiles of kPlanTile messages, 16 consecutive per thread; tmax[t] = the
-// largest offset of tiles before t (k_fold_tilemax, then k_fold_tilescan).
+// Tiles of kPlanTile messages, 16 consecutive per thread; the largest offset of
+// the tiles before a tile comes from the insert's own look-back (tile_lookback).
 //
 // A thread's run of 16 consecutive messages is 128 bytes of off and 128 of len:
 // with a.vec (both arrays 16-byte aligned) it loads as eight 16-byte vectors
@@ -377,103 +376,6 @@ __device__ __forceinline__ void load_run(const uint64_t* __restrict__ p, uint64_
   } else {
 #pragma unroll
     for (uint32_t r = 0; r < kPlanItems; ++r) v[r] = base + r < n ? p[base + r] : 0;
-  }
-}
-
-// With the early head (a.long_blocks) the same pass also reads the tile's
-// lengths and sizes it for k_fold_tilescan's decision: the tile's short
-// messages' blocks (the lane kernel's share, without the distinct long
-// payloads) and its longest chain, into tsum.
-__global__ __launch_bounds__(256) void k_fold_tilemax(FoldArgs a) {
-  __shared__ uint64_t part[256];
-  __shared__ unsigned long long s_sum[4], s_max[4];
-  const uint64_t base = (uint64_t)blockIdx.x * kPlanTile + (uint64_t)threadIdx.x * kPlanItems;
-  uint64_t o[kPlanItems];
-  load_run(a.off, base, a.n, a.vec, o);
-  uint64_t m = 0;
-#pragma unroll
-  for (uint32_t r = 0; r < kPlanItems; ++r) m = max(m, o[r]);
-  part[threadIdx.x] = m;
-  const bool sizes = a.long_blocks && !a.early_fork;  // else k_fold_longs_gate decides
-  if (sizes) {
-    uint64_t l[kPlanItems];
-    load_run(a.len, base, a.n, a.vec, l);
-    uint64_t sum = 0, mx = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < kPlanItems; ++r) {
-      const uint64_t blocks = base + r < a.n ? dev_blocks_for(l[r]) : 0;
-      mx = max(mx, blocks);
-      if (blocks < a.long_blocks) sum += blocks;
-    }
-    for (uint32_t d = 32; d > 0; d >>= 1) {  // wave sums, then one LDS word per wave
-      sum += __shfl_xor(sum, d);
-      mx = max(mx, (uint64_t)__shfl_xor(mx, d));
-    }
-    if (__lane_id() == 0) s_sum[threadIdx.x >> 6] = sum, s_max[threadIdx.x >> 6] = mx;
-  }
-  __syncthreads();
-  for (uint32_t d = 128; d > 0; d >>= 1) {
-    if (threadIdx.x < d) part[threadIdx.x] = max(part[threadIdx.x], part[threadIdx.x + d]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    a.tmax[blockIdx.x] = part[0];
-    if (sizes) {
-      a.tsum[2 * blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-      a.tsum[2 * blockIdx.x + 1] = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
-    }
-  }
-}
-
-// One workgroup: the exclusive prefix max of the tile maxima and, with the early
-// head, a first decision: when the short messages' blocks alone -- x
-// wave_block_cycles over the SIMDs -- keep the lane kernel busy past the
-// longest chain on the head (c5 on one GPU: ~60 M blocks against one 1,427-block
-// chain), the early head cannot pay and stands down before listing anything
-// (info[6] = 0; k_fold_longs then returns at once). Otherwise info[6] = 1 and
-// k_fold_longs lists and claims the long payloads and decides on the exact rule.
-__global__ __launch_bounds__(1024) void k_fold_tilescan(FoldArgs a, uint64_t tiles) {
-  __shared__ uint64_t part[1024];
-  __shared__ unsigned long long s_sum[16], s_max[16];
-  const uint32_t t = threadIdx.x;
-  const uint64_t per = (tiles + 1023) / 1024;
-  const uint64_t b0 = min((uint64_t)t * per, tiles), b1 = min(b0 + per, tiles);
-  const bool sizes = a.long_blocks && !a.early_fork;  // else k_fold_longs_gate decides
-  uint64_t m = 0, sum = 0, mx = 0;
-  for (uint64_t b = b0; b < b1; ++b) {
-    m = max(m, a.tmax[b]);
-    if (sizes) {
-      sum += a.tsum[2 * b];
-      mx = max(mx, a.tsum[2 * b + 1]);
-    }
-  }
-  part[t] = m;
-  if (sizes) {
-    for (uint32_t d = 32; d > 0; d >>= 1) {
-      sum += __shfl_xor(sum, d);
-      mx = max(mx, (uint64_t)__shfl_xor(mx, d));
-    }
-    if (__lane_id() == 0) s_sum[t >> 6] = sum, s_max[t >> 6] = mx;
-  }
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024; d <<= 1) {  // inclusive prefix max
-    const uint64_t v = t >= d ? part[t - d] : 0ull;
-    __syncthreads();
-    part[t] = max(part[t], v);
-    __syncthreads();
-  }
-  uint64_t run = t ? part[t - 1] : 0ull;  // exclusive
-  for (uint64_t b = b0; b < b1; ++b) {
-    const uint64_t v = a.tmax[b];
-    a.tmax[b] = run;
-    run = max(run, v);
-  }
-  if (sizes && t == 0) {
-    unsigned long long ss = 0, sm = 0;
-    for (int w = 0; w < 16; ++w) ss += s_sum[w], sm = max(sm, s_max[w]);
-    const uint64_t t_body = ss * a.wave_block_cycles / (64ull * a.simds);
-    const uint64_t t_head = sm * a.early_cycles;
-    a.info[6] = sm >= a.long_blocks && t_body < t_head ? 1u : 0u;
   }
 }
 
@@ -571,8 +473,9 @@ __device__ __forceinline__ void fold_hist_flush(const FoldArgs& a, FoldHist& h, 
 // stride), and the candidates' list is appended and the histogram counted
 // wave-aggregated.
 
-// Round 6: the tile prefix inside the insert (FoldArgs::tstat), a decoupled
-// look-back: each tile posts its own largest offset (kTileAgg) as soon as it has
+// The tile prefix is found inside the insert (FoldArgs::tstat) by a decoupled
+// look-back (a separate two-kernel prefix pass lost: DESIGN.md §(d) "The folded
+// planner"): each tile posts its own largest offset (kTileAgg) as soon as it has
 // it, then wave 0 combines the posts of the tiles before it, 64 a step, back to
 // the nearest tile that has posted its inclusive prefix (kTileIncl), and posts
 // its own. A post is 62 bits of offset (an arena offset past 2^62 bytes is
@@ -662,10 +565,10 @@ __global__ __launch_bounds__(256, 4) void k_fold_insert(FoldArgs a) {
   uint64_t run = (uint64_t)__shfl_up((unsigned long long)incl, 1);
   if (lane == 0) run = 0;
   for (uint32_t w = 0; w < wave; ++w) run = max(run, wmax[w]);  // max offset before this thread's run
-  // Round 6: the tile's own largest offset is posted before anything else, and the
+  // The tile's own largest offset is posted before anything else, and the
   // look-back (wave 0, after its share of the first pass) then overlaps the other
   // waves' first pass; the tiles before this one are applied in a second pass.
-  if (a.tstat && threadIdx.x == 0) {
+  if (threadIdx.x == 0) {
     const uint64_t own = min(max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])), kTileVal);
     __hip_atomic_store(&a.tstat[blockIdx.x], (blockIdx.x ? kTileAgg : kTileIncl) | own, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
@@ -709,9 +612,7 @@ __global__ __launch_bounds__(256, 4) void k_fold_insert(FoldArgs a) {
   }
   if (wave == 0) {
     uint64_t b = 0;
-    if (!a.tstat) {
-      b = a.tmax[blockIdx.x];
-    } else if (blockIdx.x) {
+    if (blockIdx.x) {
       b = tile_lookback(a, blockIdx.x);
       if (threadIdx.x == 0) {
         const uint64_t own = min(max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])), kTileVal);
@@ -761,12 +662,6 @@ __global__ __launch_bounds__(256, 4) void k_fold_insert(FoldArgs a) {
       rp = fold_claim(a, i, a.off[i], ln);
       if (rp == (uint32_t)i) fold_hist_add(hist, ln);
       trep[trep_at(li)] = rp == (uint32_t)i ? (uint16_t)fold_key(ln) : (uint16_t)0xFFFFu;
-      // (insert_list) a long payload's claimant is the early head's: listed here, as
-      // k_fold_longs would (every long message is a candidate, so every long lane)
-      if (a.insert_list && rp == (uint32_t)i && dev_blocks_for(ln) >= a.long_blocks) {
-        const uint32_t k = atomicAdd(&a.info[2], 1u);
-        if (k < a.long_cap) a.longs[k] = (uint32_t)i;
-      }
     }
     const bool folded = c < nc && rp != (uint32_t)i;
     const uint64_t fm = __ballot(folded);
@@ -845,8 +740,8 @@ __device__ __forceinline__ uint64_t key_sum_blocks(const FoldArgs& a, uint32_t k
 // The cut with the smallest T wins. Cuts whose T is the head's own term tie on
 // it, and among them the one whose lane-kernel part -- max(body, longest
 // remaining chain) -- leaves the most room wins: the cost is T + that part / 8
-// (ties after that: the smaller head; MSHA_PLAN_TIEBREAK=0: T alone, round 3's
-// rule -- equal on c5's slices, profiles/r04_tiebreak/). What moved c5 at 8
+// (ties after that: the smaller head; T alone, round 3's rule, measured equal
+// on c5's slices, profiles/r04_tiebreak/). What moved c5 at 8
 // GPUs was the two-lane head's calibration (3,800 -> 3,500 cycles a block):
 // at 3,800 the model saw room under the head for the 652-block EpochChange
 // payloads on the lane kernel, whose chain then ended ~0.12 ms after the
@@ -865,10 +760,9 @@ __device__ __forceinline__ uint64_t head_cost(const FoldArgs& a, uint64_t h, uin
   const uint64_t t_body =
       (uint64_t)((double)((btot - bh) * a.wave_block_cycles) / (double)(64ull * 4 * (cus - hcus)));
   const uint64_t t_lanes = max(t_body, next_blocks * a.lane_cycles);
-  // work-stealing lane kernel: a cut that leaves a long chain on it loses to any
-  // that does not (FoldArgs::ws_long)
-  const uint64_t ws_penalty = a.ws_long && next_blocks >= a.ws_long ? (1ull << 36) : 0;
-  return max(t_head, t_lanes) + (a.tiebreak ? t_lanes / 8 : 0) + ws_penalty;
+  // (no extra term keeps long chains off the work-stealing lane kernel: every
+  // threshold tried lost to this cost alone, DESIGN.md §(d), profiles/r06_ws2/)
+  return max(t_head, t_lanes) + t_lanes / 8;
 }
 
 constexpr uint64_t kCostMax = (uint64_t(1) << 40) - 1;
@@ -881,10 +775,9 @@ __global__ __launch_bounds__(1024) void k_fold_scan(FoldArgs a) {
   __shared__ uint32_t w_cnt[16], w_min[16], w_h[16];
   __shared__ uint64_t w_blk[16], w_key[16];
   __shared__ uint32_t s_long;  // lanes of >= long_blocks blocks
-  __shared__ unsigned long long s_long_blocks;  // and their blocks
   PLAN_STAMP(kPsScan, 0);
   const uint32_t t = threadIdx.x, lane = __lane_id(), wave = t >> 6;
-  if (t == 0) s_long = 0, s_long_blocks = 0;
+  if (t == 0) s_long = 0;
   constexpr uint32_t per = (kFoldBuckets + 1023) / 1024;
   const uint32_t b0 = min(t * per, kFoldBuckets);
   uint32_t c[per];
@@ -933,7 +826,7 @@ __global__ __launch_bounds__(1024) void k_fold_scan(FoldArgs a) {
   for (uint32_t k = 0; k < per; ++k) {  // cut before bucket b: h = run, its longest = bucket b
     const uint32_t b = b0 + k;
     if (b >= kFoldBuckets) break;
-    if (b == klong) s_long = run, s_long_blocks = brun;
+    if (b == klong) s_long = run;
     if (c[k] && a.head_cap) {
       const uint64_t cost = head_cost(a, run, brun, btot, max_blocks, key_max_blocks(a, b));
       const uint64_t key = (min(cost, kCostMax) << 20) | b;
@@ -984,18 +877,6 @@ __global__ __launch_bounds__(1024) void k_fold_scan(FoldArgs a) {
     a.info[0] = lanes;
     a.info[16] = s_long;
     a.info[17] = late;
-    if (a.insert_list) {
-      // The early head listed by the insert: always (every distinct long payload the
-      // list holds), on the eight-lane kernel when its chain is the call's long pole
-      // -- the lanes' other blocks over the SIMDs take less -- else the two-lane one
-      const uint32_t c = a.info[2];
-      const uint64_t t_body = (btot - s_long_blocks) * a.wave_block_cycles / (64ull * a.simds);
-      const bool pole = t_body < max_blocks * a.early_cycles;
-      const uint32_t e = c <= a.long_cap ? c : 0u;
-      a.info[4] = e;
-      a.info[20] = pole ? e : 0u;
-      a.info[21] = pole ? 0u : e;
-    }
     PLAN_STAMP(kPsScan, 1);
   }
 }
@@ -1024,7 +905,7 @@ __global__ __launch_bounds__(256) void k_fold_scatter(FoldArgs a) {
 #else  // round 5's committed rule, for the check's regression test (tools/r05_race.sh)
     const uint32_t early = a.long_blocks ? a.info[4] : 0u;
 #endif
-    const uint32_t late = a.early_only ? 0u : a.info[17];  // (early_only: no late head)
+    const uint32_t late = a.info[17];
     a.info[1] = early ? early : late;
     a.info[5] = early ? 0u : late;
   }
@@ -1105,13 +986,13 @@ __device__ __forceinline__ bool grid_reduce_last(uint32_t* ws, uint64_t sum, uin
 // The early head's list: every message of >= long_blocks blocks claims its
 // (off, len) in the alias table (a hot payload costs a cached read after the
 // first claim); each claimant -- one per distinct long payload -- is listed. It
-// runs beside k_fold_insert, after the tile prefix: whichever claims a key
+// runs beside k_fold_insert, after the gate: whichever claims a key
 // first, both read the same claimant back, and the claimant, a long message
 // itself, lists itself here. The last workgroup to finish publishes the list's
 // length as the early head, or 0 when it is longer than long_cap or the lane
 // kernel's share -- every short message's blocks plus the distinct long ones --
 // outlasts the head's chain anyway (then the scan's cut decides, as without it).
-// k_fold_tilescan already stood it down (info[6] == 0) when the short blocks
+// k_fold_longs_gate already stood it down (info[6] == 0) when the short blocks
 // alone do: then every workgroup returns at once (c5 on one GPU: round 4 ran
 // the whole list, 110-234 us of claims beside the insert, to stand down).
 // Round 5: a workgroup takes tiles of kPlanTile consecutive messages, loads each
@@ -1119,7 +1000,7 @@ __device__ __forceinline__ bool grid_reduce_last(uint32_t* ws, uint64_t sum, uin
 // LDS, and its threads then claim them side by side (round 4 claimed in the
 // stride loop: every wave's load -> compare chain once per iteration).
 __global__ __launch_bounds__(256) void k_fold_longs(FoldArgs a) {
-  if (a.info[6] == 0) return;  // uniform: the first decision (k_fold_tilescan or k_fold_longs_gate)
+  if (a.info[6] == 0) return;  // uniform: the first decision (k_fold_longs_gate)
   __shared__ uint32_t list[kPlanTile];
   __shared__ uint32_t nlist;
   __shared__ unsigned long long s_sum, s_max;
@@ -1173,22 +1054,18 @@ __global__ __launch_bounds__(256) void k_fold_longs(FoldArgs a) {
     const uint64_t t_body = tot * a.wave_block_cycles / (64ull * a.simds);
     const uint64_t t_head = lng * a.early_cycles;
     const bool pole = t_body < t_head;  // the head's chain outlasts the lane kernel's share
-    if (a.early_only) {
-      const uint32_t e = c <= a.long_cap ? c : 0u;
-      a.info[4] = e;
-      a.info[20] = pole ? e : 0u;
-      a.info[21] = pole ? 0u : e;
-    } else {
-      a.info[4] = c <= a.long_cap && pole ? c : 0u;
-    }
+    a.info[4] = c <= a.long_cap && pole ? c : 0u;
   }
 }
 
-// The early head's first decision without the tile prefix (FoldArgs::early_fork):
-// one pass over len alone -- the short messages' blocks (the lane kernel's share
-// without the long payloads) and the longest chain -- and the last workgroup to
-// finish decides as k_fold_tilescan would (info[6]). It runs first on the head's
-// stream, forked right after the planner's memsets, beside k_fold_tilemax.
+// The early head's first decision: one pass over len alone -- the short messages'
+// blocks (the lane kernel's share without the long payloads) and the longest
+// chain. The last workgroup to finish decides (info[6]): when the short messages'
+// blocks alone -- x wave_block_cycles over the SIMDs -- keep the lane kernel busy
+// past the longest chain on the head (c5 on one GPU: ~60 M blocks against one
+// 1,427-block chain), the early head cannot pay and stands down before listing
+// anything. It runs first on the head's stream, forked right after the planner's
+// memsets, beside the insert.
 __global__ __launch_bounds__(256) void k_fold_longs_gate(FoldArgs a) {
   __shared__ unsigned long long s_sum, s_max;
   PLAN_STAMP(kPsGate, 0);
@@ -1220,27 +1097,23 @@ __global__ __launch_bounds__(256) void k_fold_longs_gate(FoldArgs a) {
   if (threadIdx.x == 0 && grid_reduce_last(a.grid_ws + kGridWords, s_sum, s_max, ss, sm)) {
     const uint64_t t_body = ss * a.wave_block_cycles / (64ull * a.simds);
     const uint64_t t_head = sm * a.early_cycles;
-    a.info[6] = sm >= a.long_blocks && (a.early_only || t_body < t_head) ? 1u : 0u;
+    a.info[6] = sm >= a.long_blocks && t_body < t_head ? 1u : 0u;
   }
   PLAN_STAMP(kPsGate, 1);
 }
 
 hipError_t launch_fold_longs(const FoldArgs& a, int cus, hipStream_t st) {
   if (a.n == 0 || !a.long_blocks) return hipSuccess;
-  // a.longs_wgs (A/B): fewer workgroups, fewer of the same-address atomics that end
-  // each one (each costs ~20 ns serialised: profiles/r06_call4/)
+  // the list on 4 workgroups a CU (other counts: DESIGN.md §(d), profiles/r06_call4/)
   const uint64_t tiles = (a.n + kPlanTile - 1) / kPlanTile;
-  const uint64_t cap = a.longs_wgs ? a.longs_wgs : (uint64_t)cus * 4;
-  const unsigned grid = (unsigned)std::min<uint64_t>(tiles, cap);
-  // the gate on 64 workgroups unless MSHA_GATE_WGS says otherwise: each ends in
-  // same-address atomics (1,024 of them: ~60 us serialised beside the prefix,
-  // profiles/r06_call4/); partials summed by k_fold_longs instead cost the insert
-  // more bandwidth than they saved (round 6, profiles/r06_plan5/)
+  const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)cus * 4);
+  // the gate on 64 workgroups: each ends in same-address atomics (1,024 of them:
+  // ~60 us serialised, profiles/r06_call4/); partials summed by k_fold_longs
+  // instead cost the insert more bandwidth than they saved (profiles/r06_plan5/)
   // (a batch of at most a tile a CU: one workgroup a tile -- an N = 8 rank's gate ran
   // its 4 tiles a workgroup one after another, 27 us before the list could start)
-  const unsigned ggrid = (unsigned)std::min<uint64_t>(
-      tiles, a.gate_wgs ? a.gate_wgs : (tiles <= (uint64_t)cus ? (uint64_t)cus : 64u));
-  if (a.early_fork) hipLaunchKernelGGL(k_fold_longs_gate, dim3(ggrid), dim3(256), 0, st, a);
+  const unsigned ggrid = (unsigned)std::min<uint64_t>(tiles, tiles <= (uint64_t)cus ? (uint64_t)cus : 64u);
+  hipLaunchKernelGGL(k_fold_longs_gate, dim3(ggrid), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_fold_longs, dim3(grid), dim3(256), 0, st, a);
   return hipGetLastError();
 }
@@ -1268,26 +1141,14 @@ __global__ __launch_bounds__(256) void k_fold_fill(FoldArgs a, uint8_t* __restri
   PLAN_STAMP(kPsFill, 1);
 }
 
-hipError_t launch_fold_prefix(const FoldArgs& a, hipStream_t st) {
-  if (a.n == 0 || !a.table || a.tstat) return hipSuccess;  // (tstat: the insert looks back itself)
-  const unsigned ptiles = (unsigned)((a.n + kPlanTile - 1) / kPlanTile);
-  hipLaunchKernelGGL(k_fold_tilemax, dim3(ptiles), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(k_fold_tilescan, dim3(1), dim3(1024), 0, st, a, (uint64_t)ptiles);
-  return hipGetLastError();
-}
-
 hipError_t launch_fold_plan(const FoldArgs& a, hipStream_t st, hipStream_t sst, hipEvent_t fork,
-                            hipEvent_t scatter_after, hipEvent_t after_scan) {
+                            hipEvent_t scatter_after) {
   if (a.n == 0) return hipSuccess;
   const unsigned ptiles = (unsigned)((a.n + kPlanTile - 1) / kPlanTile);
   if (a.table) hipLaunchKernelGGL(k_fold_insert, dim3(ptiles), dim3(256), 0, st, a);
   const unsigned ftiles = (unsigned)((a.n + kFoldTile - 1) / kFoldTile);
   if (!a.table) hipLaunchKernelGGL(k_fold_keys, dim3(ftiles), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_fold_scan, dim3(1), dim3(1024), 0, st, a);
-  if (after_scan) {
-    const hipError_t e = hipEventRecord(after_scan, st);
-    if (e != hipSuccess) return e;
-  }
   if (sst != st) {
     hipError_t e = hipEventRecord(fork, st);
     if (e == hipSuccess) e = hipStreamWaitEvent(sst, fork, 0);

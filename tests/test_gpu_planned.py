@@ -60,11 +60,6 @@ def _chain8():
     return os.environ.get("MSHA_HEAD_CHAIN8", "1") != "0"
 
 
-def _insert_list():
-    """Does the insert list the early head, with no late head (MSHA_INSERT_LIST=1, A/B)?"""
-    return os.environ.get("MSHA_INSERT_LIST", "0") == "1"
-
-
 def _assert_head_kernels(before, after, fold):
     """Each head launch counted by its kernel (ABI 10): folded, the early head on
     k_digest_chain8 (k_digest_chain2 under MSHA_HEAD_CHAIN8=0) and the scan's cut on
@@ -72,9 +67,7 @@ def _assert_head_kernels(before, after, fold):
     early head back to the two-lane kernel fails here."""
     c2, c8 = _delta(before, after, "launches_chain2"), _delta(before, after, "launches_chain8")
     if fold and _early(fold):
-        # (MSHA_INSERT_LIST=1, A/B: no late head; the early head on one kernel when
-        # the eight-lane one is off, else both launched, one armed)
-        assert (c8, c2) == ((1, 1) if _chain8() else ((0, 1) if _insert_list() else (0, 2))), (c8, c2)
+        assert (c8, c2) == ((1, 1) if _chain8() else (0, 2)), (c8, c2)
     elif fold:
         assert (c8, c2) == (0, 1), (c8, c2)
     else:
@@ -147,7 +140,7 @@ def test_early_head_kernel_counted(engine, monkeypatch, chain8):
     assert np.array_equal(_run(engine, w, True), _expect(w))
     after = engine.stats()
     c2, c8 = _delta(before, after, "launches_chain2"), _delta(before, after, "launches_chain8")
-    assert (c8, c2) == ((1, 1) if chain8 is None else ((0, 1) if _insert_list() else (0, 2))), (c8, c2)
+    assert (c8, c2) == ((1, 1) if chain8 is None else (0, 2)), (c8, c2)
 
 
 @pytest.mark.parametrize("pct", ["1", "100000"])
@@ -427,14 +420,9 @@ def test_early_head_batches(engine, monkeypatch, case):
     _assert_head_kernels(before, engine.stats(), True)
 
 
-@pytest.mark.parametrize("lookback", ["1", "0"])
-def test_tile_backrefs(engine, monkeypatch, lookback):
-    """Candidates-first folding across tiles: a message skips the alias table only
-    when its offset is above every earlier message's, which the tile prefix carries
-    from tile to tile -- the insert's own look-back (default) or k_fold_tilemax and
-    k_fold_tilescan (MSHA_FOLD_LOOKBACK=0). Here every tile of 4,096 messages names
-    payloads of the tile before it again (10 % of its messages). Every digest exact."""
-    monkeypatch.setenv("MSHA_FOLD_LOOKBACK", lookback)
+@pytest.fixture(scope="module")
+def backrefs():
+    """Every tile of 4,096 messages names payloads of the tile before it again (10 %)."""
     rng = np.random.default_rng(0x1B)
     n = 300_000
     ln = rng.integers(0, 700, n).astype(np.uint64)
@@ -443,28 +431,40 @@ def test_tile_backrefs(engine, monkeypatch, lookback):
     src = np.clip(np.arange(n) - 4096 - rng.integers(0, 4096, n), 0, n - 1)
     off[back], ln[back] = off[src[back]], ln[src[back]]
     w = W.Workload("tile-backrefs", arena, off, ln)
-    assert np.array_equal(_run(engine, w, True), _expect(w))
+    return w, _expect(w)
 
 
-@pytest.mark.parametrize("world", [1, 8])
-def test_lookback_folds_as_the_prefix(engine, monkeypatch, capfd, world):
-    """The insert's tile look-back hands every tile the same threshold as the
-    two-kernel prefix: a c5 slice folded both ways has the same number of lanes
-    (MSHA_TRACE_PLAN prints the GPU's plan; lanes = fresh messages + one claimant per
-    repeated payload, independent of which message wins a claim), digests exact."""
-    w = W.c5_storm(n=(1 << 23) // world)
-    exp = _expect(w)
+def test_tile_backrefs(engine, backrefs):
+    """Candidates-first folding across tiles: a message skips the alias table only when its offset
+    is above every earlier message's, carried from tile to tile by the insert's look-back."""
+    assert np.array_equal(_run(engine, backrefs[0], True), backrefs[1])
+
+
+def _model_lanes(w):
+    """The folded planner's lane count (plan.hip k_fold_insert) on the host: a message is
+    fresh, a lane without a claim, when it is not long (>= 256 blocks: the early head's) and
+    its offset is strictly above every earlier one's (message 0 counts as above); the others
+    claim (off, len) in the alias table, one claimant per distinct key a lane."""
+    blocks = (w.len >> np.uint64(6)) + np.where((w.len & np.uint64(63)) < 56, 1, 2).astype(np.uint64)
+    off = w.off.astype(np.int64)
+    fresh = (blocks < 256) & (off > np.r_[-1, np.maximum.accumulate(off)[:-1]])
+    return int(fresh.sum()) + len(np.unique(np.stack([w.off[~fresh], w.len[~fresh]], 1), axis=0))
+
+
+@pytest.mark.parametrize("case", ["backrefs", "c5"])
+def test_lanes_match_host_model(engine, monkeypatch, capfd, backrefs, case):
+    """A folded call's lane count (MSHA_TRACE_PLAN prints the GPU's plan) equals the host
+    model's, digests exact: the tile-backrefs workload, the only one here whose earlier tiles
+    demote messages in the insert's second pass (297,895 lanes = 269,840 fresh + 28,055
+    claimants), and a c5 slice (996,126 lanes; 50,434 long messages fold to 100 claimants)."""
+    w = backrefs[0] if case == "backrefs" else W.c5_storm(n=1 << 20)
+    want = _model_lanes(w)
+    assert want == {"backrefs": 297_895, "c5": 996_126}[case]
     monkeypatch.setenv("MSHA_TRACE_PLAN", "1")
-    lanes = {}
-    for lb in ("1", "0"):
-        monkeypatch.setenv("MSHA_FOLD_LOOKBACK", lb)
-        capfd.readouterr()
-        assert np.array_equal(_run(engine, w, True), exp)
-        err = capfd.readouterr().err
-        lines = [l for l in err.splitlines() if "planned device call" in l]
-        assert len(lines) == 1, err
-        lanes[lb] = int(lines[0].split(",")[1].split()[0])
-    assert lanes["1"] == lanes["0"] and 0 < lanes["1"] < w.n, lanes
+    capfd.readouterr()
+    assert np.array_equal(_run(engine, w, True), backrefs[1] if case == "backrefs" else _expect(w))
+    lines = [l for l in capfd.readouterr().err.splitlines() if "planned device call" in l]
+    assert len(lines) == 1 and int(lines[0].split(",")[1].split()[0]) == want, lines
 
 
 def test_lookback_give_up_exact(engine, monkeypatch):
