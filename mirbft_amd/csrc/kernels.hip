@@ -1883,8 +1883,8 @@ hipError_t launch_digest_batch(const uint8_t* arena, const uint64_t* off, const 
     return hipGetLastError();
   }
   if (uses_coop(n, cus, policy) && !head) {
-    static const int small8 = env_int("MSHA_SMALL_CHAIN8", 1);
-    if (policy == 0 && n <= (uint64_t)cus * kChain8MsgsPerWg && small8) {
+    // (both knobs read per call: a getenv is ~0.1 us, and tests switch them in one process)
+    if (policy == 0 && n <= (uint64_t)cus * kChain8MsgsPerWg && env_int("MSHA_SMALL_CHAIN8", 1)) {
       // AUTO, at most 16 messages per CU (a call of a few actions: the latency
       // path): the eight-lane chain, one workgroup per CU (64 KiB of dynamic LDS
       // on top of its 64 KiB keeps a second one off the CU). MSHA_SMALL_CHAIN8=0:
