@@ -290,6 +290,96 @@ int msha_pinned_alloc(msha_ctx* ctx, uint64_t bytes, void** p);
 int msha_pinned_free(msha_ctx* ctx, void* p);
 
 /*
+ * Stream sets: many resumable SHA-256 streams with hash.Hash semantics, the
+ * streaming half of processor.Hasher (New() hash.Hash, pkg/processor/serial.go:21-23):
+ * Write appends, Sum(b) appends the digest of everything written so far and
+ * changes nothing. The reference streams in NodeState (pkg/testengine/recorder.go:
+ * 288-359: Apply writes each committed digest into ActiveHash as it arrives, Snap
+ * takes Sum(nil) and starts a new hash from it); the same shape serves per-client
+ * running hashes, or a message set whose bytes arrive in pieces or do not fit one
+ * arena. The GPU gains from parallelism ACROSS streams: one stream is one lane,
+ * so a lone stream runs at one lane's rate (tens of MB/s). ABI 10, additive:
+ * MSHA_HAS_STREAMS tells a build that has them.
+ *
+ * A set keeps, per stream, the 8-word chaining state on the context's first
+ * device and, on the host, the byte count and the buffered tail of fewer than 64
+ * bytes; the GPU never sees a partial block. A set must be destroyed before its
+ * context; calls on it take the context's lock. After a HIP error a set is
+ * failed: every call returns MSHA_ERR_HIP until msha_streams_reset(set, NULL, 0).
+ * There is no CPU fallback: Sum runs on the GPU as well.
+ */
+#define MSHA_HAS_STREAMS 1
+/* Bytes of one exported stream: "sha\x03", the 8 state words big-endian, 64
+ * buffer bytes (zero past length % 64), the length as a big-endian uint64. The
+ * layout is meant to equal Go crypto/sha256's MarshalBinary
+ * (encoding.BinaryMarshaler), so a half-hashed state could pass between this
+ * engine and a Go hash.Hash; with no Go toolchain where this was built that
+ * equality is UNVERIFIED. */
+#define MSHA_STREAM_STATE_BYTES 108u
+typedef struct msha_streams msha_streams;
+/* n streams in New() state (recorder.go:420, Hasher.New()) on the context's first
+ * device. staging_bytes bounds the pinned and device staging one piece of a write
+ * may use (0: 64 MiB; min 4096; rounded to 64): memory stays bounded by it
+ * whatever a call's size. n < 2^32. */
+int msha_streams_create(msha_ctx* ctx, uint64_t n, uint64_t staging_bytes, msha_streams** out);
+void msha_streams_destroy(msha_streams* set);
+/* Write (hash.Hash.Write; recorder.go:348, ActiveHash.Write(digest)): for j in call
+ * order, stream id[j] appends arena[off[j] : off[j]+len[j]]. An id may repeat; its
+ * chunks append in order. Everything is validated first (ids below n, ranges
+ * inside the arena): a bad argument returns MSHA_ERR_INVALID_ARG and changes no
+ * stream. A call that leaves every touched stream under one block launches
+ * nothing. */
+int msha_streams_write(msha_streams* set, const uint8_t* arena, uint64_t arena_len,
+                       const uint64_t* id, const uint64_t* off, const uint64_t* len, uint64_t k);
+/* Sum(nil) (recorder.go:298): out[32 j] = SHA-256 of everything written to id[j];
+ * no stream changes. id NULL: all n streams, k == n. */
+int msha_streams_sum(msha_streams* set, const uint64_t* id, uint64_t k, uint8_t* out);
+/* Reset (hash.Hash.Reset; recorder.go:299, a new hash per checkpoint): the streams
+ * return to New() state. id NULL: all, and a failed set is usable again. */
+int msha_streams_reset(msha_streams* set, const uint64_t* id, uint64_t k);
+/* out[j] = bytes written to id[j] so far (id NULL: all n streams, k == n). */
+int msha_streams_length(const msha_streams* set, const uint64_t* id, uint64_t k, uint64_t* out);
+/* MarshalBinary / UnmarshalBinary of the streams id[j] (id NULL: all, k == n):
+ * k x MSHA_STREAM_STATE_BYTES bytes. Import ignores buffer bytes past length % 64
+ * and rejects a wrong magic (MSHA_ERR_INVALID_ARG, no stream changed). */
+int msha_streams_export(msha_streams* set, const uint64_t* id, uint64_t k, uint8_t* out);
+int msha_streams_import(msha_streams* set, const uint64_t* id, uint64_t k, const uint8_t* in);
+typedef struct {
+  uint64_t writes;               /* msha_streams_write calls completed */
+  uint64_t sums;                 /* msha_streams_sum calls completed */
+  uint64_t bytes_written;
+  uint64_t blocks_absorbed;      /* whole blocks compressed by the absorb kernel */
+  uint64_t blocks_finished;      /* tail and length blocks compressed by the finish kernel */
+  uint64_t launches_absorb;
+  uint64_t launches_finish;
+  uint64_t buffered_only_writes; /* writes that launched nothing (every touched stream under one block) */
+  uint64_t pieces;               /* staging pieces uploaded by writes */
+  uint32_t last_load_mode;       /* load mode of the last absorb / finish launch (1 prefetch, 2 paired) */
+  uint32_t last_lanes;           /* its lanes */
+  double last_kernel_ms;         /* its kernel time (HIP events) */
+} msha_streams_stats;
+int msha_streams_get_stats(const msha_streams* set, msha_streams_stats* out);
+/*
+ * Device-resident forms of the two primitives the sets run on, same rules as
+ * msha_digest_batch_device (device memory of the context's first device, starts
+ * MSHA_DEVICE_ALIGN-aligned, MSHA_DEVICE_ARENA_SLACK readable bytes after the last
+ * lane's bytes, errors through msha_device_status); they return after enqueueing.
+ * Absorb (Write of whole blocks): lane i compresses d_nblocks[i] 64-byte blocks at
+ * d_arena + d_off[i] into d_state[8 i .. 8 i + 8) (host-order words, in/out; a New()
+ * stream holds the FIPS 180-4 initial value). A lane with no block, or with a
+ * misaligned start, leaves its state as it was.
+ * Finish (Sum): d_out[32 i] = the digest of a message whose first d_prefix[i]
+ * bytes (a multiple of 64; NULL: 0) are in d_state[8 i ..] (NULL: the initial
+ * value) and whose last d_len[i] bytes are at d_arena + d_off[i]; the state is not
+ * written. With both NULL this is msha_digest_batch_device.
+ */
+int msha_absorb_device(msha_ctx* ctx, uint32_t* d_state, const uint8_t* d_arena,
+                       const uint64_t* d_off, const uint64_t* d_nblocks, uint64_t n, void* stream);
+int msha_finish_device(msha_ctx* ctx, const uint32_t* d_state, const uint64_t* d_prefix,
+                       const uint8_t* d_arena, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
+                       uint8_t* d_out, void* stream);
+
+/*
  * Host-only helpers (no GPU needed).
  * msha_blocks_for_len: number of 64-byte compressions for an L-byte message,
  *   floor(L/64) + (L%64 < 56 ? 1 : 2)  (FIPS 180-4 5.1.1 padding).

@@ -8,10 +8,12 @@ from .engine import Engine, MshaError, blocks_for_len, device_count, pack_parts,
 from .processor import (Action, ActionHashRequest, ActionList, EventHashResult, EventList, GPUHasher,
                         HashOrigin, HashOriginBatch, HashOriginEpochChange, HashOriginVerifyBatch,
                         ProcessHashActions, ProcessorError, action_hash, checkpoint_hashes)
+from .streams import StreamSet
 
 __all__ = [
     "Engine", "MshaError", "blocks_for_len", "device_count", "pack_parts", "partition_by_blocks",
     "Action", "ActionHashRequest", "ActionList", "EventHashResult", "EventList", "GPUHasher",
     "HashOrigin", "HashOriginBatch", "HashOriginEpochChange", "HashOriginVerifyBatch",
     "ProcessHashActions", "ProcessorError", "action_hash", "checkpoint_hashes",
+    "StreamSet",
 ]

@@ -31,6 +31,7 @@ MSHA_DEVICE_ALIGN = 16
 MSHA_KERNEL_AUTO = 0
 MSHA_KERNEL_LANE = 1
 MSHA_KERNEL_COOP = 2
+MSHA_STREAM_STATE_BYTES = 108
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -100,6 +101,25 @@ class MshaClockInfo(ctypes.Structure):
     ]
 
 
+class MshaStreamsStats(ctypes.Structure):
+    _fields_ = [
+        ("writes", ctypes.c_uint64),
+        ("sums", ctypes.c_uint64),
+        ("bytes_written", ctypes.c_uint64),
+        ("blocks_absorbed", ctypes.c_uint64),
+        ("blocks_finished", ctypes.c_uint64),
+        ("launches_absorb", ctypes.c_uint64),
+        ("launches_finish", ctypes.c_uint64),
+        ("buffered_only_writes", ctypes.c_uint64),
+        ("pieces", ctypes.c_uint64),
+        ("last_load_mode", ctypes.c_uint32),
+        ("last_lanes", ctypes.c_uint32),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
+_setp = ctypes.c_void_p
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "msha_abi_version": (ctypes.c_uint32, []),
@@ -140,6 +160,20 @@ SIGNATURES = {
     "msha_order_by_blocks": (ctypes.c_int, [_u64p, ctypes.c_uint64, _u32p]),
     "msha_partition_by_blocks": (ctypes.c_int, [_u64p, ctypes.c_uint64, ctypes.c_uint32, _u64p]),
     "msha_alias_first": (ctypes.c_int, [_u64p, _u64p, ctypes.c_uint64, _u64p]),
+    "msha_streams_create": (ctypes.c_int, [_ctxp, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(_setp)]),
+    "msha_streams_destroy": (None, [_setp]),
+    "msha_streams_write": (ctypes.c_int, [_setp, _u8p, ctypes.c_uint64, _u64p, _u64p, _u64p, ctypes.c_uint64]),
+    "msha_streams_sum": (ctypes.c_int, [_setp, _u64p, ctypes.c_uint64, _u8p]),
+    "msha_streams_reset": (ctypes.c_int, [_setp, _u64p, ctypes.c_uint64]),
+    "msha_streams_length": (ctypes.c_int, [_setp, _u64p, ctypes.c_uint64, _u64p]),
+    "msha_streams_export": (ctypes.c_int, [_setp, _u64p, ctypes.c_uint64, _u8p]),
+    "msha_streams_import": (ctypes.c_int, [_setp, _u64p, ctypes.c_uint64, _u8p]),
+    "msha_streams_get_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaStreamsStats)]),
+    "msha_absorb_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "msha_finish_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
 }
 
 _lib = None
@@ -183,7 +217,8 @@ def lib() -> ctypes.CDLL:
 
 # The files msha_build_id()'s src hash covers, in the Makefile's order (SRCS).
 _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mirsha.cpp",
-              os.path.join("..", "..", "include", "mirsha.h"))
+              os.path.join("..", "..", "include", "mirsha.h"),
+              "stream_kernels.hip", "stream_pack.hpp", "ctx_access.hpp", "streams.cpp")
 
 
 def source_id() -> str:

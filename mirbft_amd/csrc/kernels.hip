@@ -102,35 +102,6 @@ namespace msha {
 #define MSHA_WAVE_STAMP_CLOSE_AT(kind, nb, at)
 #endif
 
-template <int MODE = 0>
-__device__ __forceinline__ void load_block16(const uint8_t* p, uint32_t (&raw)[16]) {
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4* q = reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const u32x4 v = q[i];
-    raw[4 * i + 0] = v.x; raw[4 * i + 1] = v.y; raw[4 * i + 2] = v.z; raw[4 * i + 3] = v.w;
-  }
-}
-
-__device__ __forceinline__ void to_words(const uint32_t (&raw)[16], uint32_t (&w)[16]) {
-#pragma unroll
-  for (int j = 0; j < 16; ++j) w[j] = bswap(raw[j]);
-}
-
-// How a lane brings its message blocks in from HBM (all modes are bit-identical):
-//  kSingle   load block b at the top of iteration b; latency hidden by the
-//            other waves of the SIMD (high occupancy)
-//  kPrefetch load block b+1 while block b is compressed (16 more live VGPRs):
-//            for few, long messages, where there are too few waves to hide it
-//  kPair     at even b load blocks b and b+1 together: both halves of a
-//            128-byte line are requested back to back, so the line is read
-//            from HBM once instead of being evicted and re-fetched between
-//            the two half-line requests (lane stride >= 128 B is the norm)
-// (Rejected after A/B, profiles/r01_ab_modes, r01_ab_nt: an LDS-DMA prefetch
-// mode, 6 % slower on c2, and nontemporal payload loads, 5-10 % slower.)
-enum LoadMode { kSingle = 0, kPrefetch = 1, kPair = 2, kPipe = 3 };
-
 // Hash one message of `len` bytes starting at p (device memory, 16-byte
 // aligned, with kArenaSlack (kernels.hpp) readable bytes after the arena's last
 // message) into out. One compress() call site: full blocks, the tail block
@@ -1751,23 +1722,6 @@ hipError_t launch_clock_probe(uint32_t blocks, uint32_t workgroups, uint64_t* st
 // Launchers (host side). Grids are one lane per message, 256-thread blocks.
 // ---------------------------------------------------------------------------
 static inline unsigned grid_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
-
-// Fewer than ~3 waves per SIMD cannot hide HBM latency by occupancy: use the
-// register-prefetching variant then; otherwise pair loads. At one wave per
-// SIMD or less the pipelined kernel (kPipe, k_digest_batch_pipe) gives the lone
-// wave independent work: c4 2.78 -> 2.64 ms; at 1.5, 2 and 3 waves per SIMD it
-// ties or loses (profiles/r01_ab_pipe/). For A/B measurements MSHA_LOAD_MODE
-// (0/1/2/3) forces the load mode.
-static inline int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-static inline int pick_mode(uint64_t n, int cus) {
-  static const int forced = env_int("MSHA_LOAD_MODE", -1);
-  if (forced >= kSingle && forced <= kPipe) return forced;
-  if (n <= (uint64_t)cus * 4 * 64) return kPipe;
-  return n < (uint64_t)cus * 4 * 64 * 3 ? kPrefetch : kPair;
-}
 
 // Cooperative chaining (AUTO) when every workgroup of the launch gets a CU of
 // its own (n <= 128 per CU): below that one lane per message leaves at least

@@ -2,12 +2,43 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 namespace msha {
 
 // Bytes that must be readable after the last message of a device arena: the
 // kernels read a message's final block as one whole 64-byte block.
 constexpr uint64_t kArenaSlack = 64;
+
+// How a lane brings its message blocks in from HBM (all modes are bit-identical):
+//  kSingle   load block b at the top of iteration b; latency hidden by the
+//            other waves of the SIMD (high occupancy)
+//  kPrefetch load block b+1 while block b is compressed (16 more live VGPRs):
+//            for few, long messages, where there are too few waves to hide it
+//  kPair     at even b load blocks b and b+1 together: both halves of a
+//            128-byte line are requested back to back, so the line is read
+//            from HBM once instead of being evicted and re-fetched between
+//            the two half-line requests (lane stride >= 128 B is the norm)
+// (Rejected after A/B, profiles/r01_ab_modes, r01_ab_nt: an LDS-DMA prefetch
+// mode, 6 % slower on c2, and nontemporal payload loads, 5-10 % slower.)
+enum LoadMode { kSingle = 0, kPrefetch = 1, kPair = 2, kPipe = 3 };
+
+// Fewer than ~3 waves per SIMD cannot hide HBM latency by occupancy: use the
+// register-prefetching variant then; otherwise pair loads. At one wave per
+// SIMD or less the pipelined kernel (kPipe, k_digest_batch_pipe) gives the lone
+// wave independent work: c4 2.78 -> 2.64 ms; at 1.5, 2 and 3 waves per SIMD it
+// ties or loses (profiles/r01_ab_pipe/). For A/B measurements MSHA_LOAD_MODE
+// (0/1/2/3) forces the load mode.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+inline int pick_mode(uint64_t n, int cus) {
+  static const int forced = env_int("MSHA_LOAD_MODE", -1);
+  if (forced >= kSingle && forced <= kPipe) return forced;
+  if (n <= (uint64_t)cus * 4 * 64) return kPipe;
+  return n < (uint64_t)cus * 4 * 64 * 3 ? kPrefetch : kPair;
+}
 
 // Lane i hashes message m = order ? order[i] : i (arena + off[m], len[m]) into
 // digest slot o = out_idx ? out_idx[i] : m (out + 32 o). The device API passes
@@ -234,6 +265,32 @@ hipError_t launch_fold_plan(const FoldArgs& a, hipStream_t st, hipStream_t sst, 
 hipError_t launch_fold_longs(const FoldArgs& a, int cus, hipStream_t st);
 // out[i] = out[rep] for every folded message (FoldArgs::apairs), after the hashing.
 hipError_t launch_fold_fill(const FoldArgs& a, uint8_t* out, hipStream_t st);
+
+// Stream sets (stream_kernels.hip): SHA-256 resumed from a chaining state. Lane i
+// works on state row r = row ? row[i] : i (state + 8 r: eight host-order words; a
+// launch names a row at most once) and on the bytes at arena + off[i] (16-byte
+// aligned, kArenaSlack readable bytes after the last lane's; a misaligned start
+// sets bit 0 of *err and the lane changes nothing / zeroes its digest).
+//  absorb: compresses nblocks[i] whole blocks, no padding, and writes the state
+//          back; a lane with no block touches nothing.
+//  finish: hashes the last len[i] bytes of a message whose first prefix[i] bytes
+//          (a multiple of 64; prefix null: 0) are in the state (state null: the
+//          IV), pads for prefix + len bytes and stores the digest at out + 32 i;
+//          the state is not written.
+// mode (may be null): the load mode the launch ran (pick_mode(n, cus); kPipe runs
+// as kPrefetch: these kernels have no software-pipelined variant).
+hipError_t launch_stream_absorb(uint32_t* state, const uint8_t* arena, const uint64_t* off,
+                                const uint64_t* nblocks, const uint32_t* row, uint64_t n, uint32_t* err,
+                                int cus, hipStream_t st, int* mode = nullptr);
+hipError_t launch_stream_finish(const uint32_t* state, const uint64_t* prefix, const uint8_t* arena,
+                                const uint64_t* off, const uint64_t* len, const uint32_t* row, uint64_t n,
+                                uint8_t* out, uint32_t* err, int cus, hipStream_t st, int* mode = nullptr);
+// State rows of a set, moved in bulk: state[row[i]] = vals ? vals[i] : the IV (row
+// null: row i), and out[i] = state[row[i]]; eight words a row.
+hipError_t launch_stream_rows_set(uint32_t* state, const uint32_t* row, const uint32_t* vals, uint64_t n,
+                                  hipStream_t st);
+hipError_t launch_stream_rows_get(const uint32_t* state, const uint32_t* row, uint32_t* out, uint64_t n,
+                                  hipStream_t st);
 
 // Clock probe (msha_clock_probe): `workgroups` x 256 lanes compress `blocks`
 // register-resident blocks each; stamps gets (memtime, memrealtime) at start and

@@ -32,6 +32,7 @@
 
 #include "../../include/mirsha.h"
 #include "kernels.hpp"
+#include "ctx_access.hpp"
 
 namespace {
 
@@ -3247,3 +3248,24 @@ int msha_pinned_free(msha_ctx* ctx, void* p) {
 }
 
 }  // extern "C"
+
+// ctx_access.hpp: the context as the stream sets (streams.cpp) reach it.
+namespace msha {
+
+std::mutex& ctx_mutex(const msha_ctx* ctx) { return ctx->mu; }
+
+int ctx_first_device(msha_ctx* ctx, CtxDevice* out) {
+  return guarded(ctx, [&] {
+    hipStream_t st;
+    device_prologue(ctx, nullptr, &st);
+    const Device& d = ctx->devs[0];
+    out->id = d.id;
+    out->cus = d.cus;
+    out->stream = st;
+    out->err = d.err.as<uint32_t>();
+  });
+}
+
+int ctx_fail(msha_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg ? msg : ""); }
+
+}  // namespace msha

@@ -203,6 +203,24 @@ __device__ __forceinline__ void length_block(uint64_t len, uint32_t (&w)[16]) {
   w[15] = (uint32_t)bits;
 }
 
+// One 64-byte block from HBM as four 16-byte loads (p 16-byte aligned); MODE is the
+// caller's load mode (kernels.hpp LoadMode), all modes load alike.
+template <int MODE = 0>
+__device__ __forceinline__ void load_block16(const uint8_t* p, uint32_t (&raw)[16]) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4* q = reinterpret_cast<const u32x4*>(p);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const u32x4 v = q[i];
+    raw[4 * i + 0] = v.x; raw[4 * i + 1] = v.y; raw[4 * i + 2] = v.z; raw[4 * i + 3] = v.w;
+  }
+}
+
+__device__ __forceinline__ void to_words(const uint32_t (&raw)[16], uint32_t (&w)[16]) {
+#pragma unroll
+  for (int j = 0; j < 16; ++j) w[j] = bswap(raw[j]);
+}
+
 // Store the digest (big-endian words) as 32 contiguous bytes.
 __device__ __forceinline__ void store_digest(const State& s, uint8_t* out) {
   uint4 lo = make_uint4(bswap(s.h[0]), bswap(s.h[1]), bswap(s.h[2]), bswap(s.h[3]));

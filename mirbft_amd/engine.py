@@ -88,6 +88,8 @@ class Engine:
     # -- lifecycle -------------------------------------------------------
     def close(self) -> None:
         if getattr(self, "_ctx", None):
+            for st in list(getattr(self, "_sets", [])):   # a set must go before its context
+                st.close()
             for p in getattr(self, "_pinned", []):
                 self._lib.msha_pinned_free(self._ctx, p)
             self._pinned = []
@@ -239,7 +241,8 @@ class Engine:
         dev = getattr(self, "_dev_index", None)
         if dev is None:
             dev = self._dev_index = self._device_index()
-        sizes = {"off": 8, "length": 8, "begin": 8, "order": 4, "idx": 4, "arena": 1, "table": 1}
+        sizes = {"off": 8, "length": 8, "begin": 8, "order": 4, "idx": 4, "arena": 1, "table": 1,
+                 "nblocks": 8, "prefix": 8, "state": 4}
         for name, t in list(tensors.items()) + [("out", out)]:
             if t is None:
                 continue
@@ -250,11 +253,14 @@ class Engine:
             want = 1 if name == "out" else sizes[name]
             if t.element_size() != want or t.is_floating_point():
                 raise ValueError(f"{name} must hold {want}-byte integers (got {t.dtype})")
-        for name in ("off", "length", "order"):
+        for name in ("off", "length", "order", "nblocks", "prefix"):
             t = tensors.get(name)
             if t is not None and t.numel() != n:
                 raise ValueError(f"{name} has {t.numel()} entries, expected {n}")
-        if out.numel() < 32 * n:
+        t = tensors.get("state")
+        if t is not None and t.numel() != 8 * n:
+            raise ValueError(f"state has {t.numel()} words, expected {8 * n}")
+        if out is not None and out.numel() < 32 * n:
             raise ValueError(f"out holds {out.numel()} bytes, needs {32 * n}")
 
     def digest_batch_device(self, arena, off, length, out, stream=None, order=None) -> None:
@@ -283,6 +289,23 @@ class Engine:
         self._check(self._lib.msha_digest_of_digests_device(self._ctx, table.data_ptr(), idx.data_ptr(),
                                                             begin.data_ptr(), begin.numel() - 1,
                                                             out.data_ptr(), self._stream_ptr(stream)))
+
+    def absorb_device(self, state, arena, off, nblocks, stream=None) -> None:
+        """msha_absorb_device: lane i compresses nblocks[i] whole 64-byte blocks at
+        arena + off[i] into state[i] (n x 8 4-byte words, host order, in/out)."""
+        self._check_device_args(off.numel(), None, state=state, arena=arena, off=off, nblocks=nblocks)
+        self._check(self._lib.msha_absorb_device(self._ctx, state.data_ptr(), arena.data_ptr(), off.data_ptr(),
+                                                 nblocks.data_ptr(), off.numel(), self._stream_ptr(stream)))
+
+    def finish_device(self, state, prefix, arena, off, length, out, stream=None) -> None:
+        """msha_finish_device: out[i] = the digest of the message whose first prefix[i]
+        bytes are in state[i] (None: the initial value, prefix None: 0) and whose last
+        length[i] bytes are at arena + off[i]."""
+        self._check_device_args(off.numel(), out, state=state, prefix=prefix, arena=arena, off=off, length=length)
+        self._check(self._lib.msha_finish_device(self._ctx, None if state is None else state.data_ptr(),
+                                                 None if prefix is None else prefix.data_ptr(),
+                                                 arena.data_ptr(), off.data_ptr(), length.data_ptr(),
+                                                 off.numel(), out.data_ptr(), self._stream_ptr(stream)))
 
     def clock_probe(self, blocks_per_lane: int = 48) -> dict:
         """msha_clock_probe: the clock the first GPU holds under the hash

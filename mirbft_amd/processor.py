@@ -187,6 +187,13 @@ class GPUHasher:
     def new(self) -> _GPUHash:
         return _GPUHash(self.engine)
 
+    def new_streams(self, n: int, staging_bytes: int = 0):
+        """n resumable hash.Hash streams on the GPU (StreamSet): for many concurrent
+        running hashes, e.g. one NodeState.ActiveHash per node (recorder.go:288-359).
+        new() stays the single buffered hash."""
+        from .streams import StreamSet
+        return StreamSet(self.engine, n, staging_bytes)
+
     def hash_batch(self, actions: Sequence[Sequence[bytes]]) -> List[bytes]:
         return self.engine.hash_actions(actions)
 
