@@ -239,8 +239,10 @@ int msha_digest_of_digests_device(msha_ctx* ctx, const uint8_t* d_table, const u
                                   const uint64_t* d_begin, uint64_t n, uint8_t* d_out,
                                   void* stream);
 /* Synchronizes the context's first device and reports (then clears) any
- * device-side error flag raised by *_device calls: MSHA_OK, MSHA_ERR_ALIGNMENT, or
- * MSHA_ERR_HIP if a split-chaining handoff (kernels.hip) waited over 100 ms. */
+ * device-side error flag raised by *_device calls: MSHA_OK, MSHA_ERR_ALIGNMENT,
+ * MSHA_ERR_HIP if a split-chaining handoff (kernels.hip) waited over 100 ms, or
+ * MSHA_ERR_INVALID_ARG for a decreasing part range given to msha_hash_actions_device
+ * (reported after the other two when several are raised). */
 int msha_device_status(msha_ctx* ctx);
 
 /*
@@ -378,6 +380,58 @@ int msha_absorb_device(msha_ctx* ctx, uint32_t* d_state, const uint8_t* d_arena,
 int msha_finish_device(msha_ctx* ctx, const uint32_t* d_state, const uint64_t* d_prefix,
                        const uint8_t* d_arena, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
                        uint8_t* d_out, void* stream);
+
+/*
+ * ProcessHashActions from HBM (serial.go:180-198), the device-resident form of
+ * msha_hash_actions (ABI 10, additive: MSHA_HAS_PARTS_DEVICE tells a build that has
+ * it). An action's Data is a list of byte slices hashed back to back; an
+ * EpochChange's interleaves 8-byte big-endian fields with 32-byte digests
+ * (stateless.go:323-352). Here the slices stay where they are in device memory:
+ *   part j           = d_arena[d_part_off[j] : d_part_off[j] + d_part_len[j]]
+ *   action i's parts = parts [d_action_part_begin[i], d_action_part_begin[i+1])
+ *   d_out[32*i ...]  = SHA-256(concatenation of action i's parts)
+ * A zero-part action hashes the empty string; empty parts contribute nothing; parts
+ * may overlap, repeat and be shared between actions. Offsets and lengths are 64-bit
+ * (an arena past 4 GiB, an action past 2^32 bytes); an action has fewer than 2^32
+ * blocks and fewer than 2^32 parts. d_action_part_begin has n_actions + 1 entries. d_order (may be NULL) is as
+ * in msha_digest_batch_device: lane i hashes action d_order[i], whose digest still
+ * lands at d_out + 32*d_order[i].
+ *
+ * Every pointer is device memory of the context's FIRST device; the call returns
+ * after enqueueing on `stream` (NULL: the context's own). It is one kernel launch, on
+ * no library stream and with no host wait, so it can be captured into a HIP graph as
+ * msha_digest_batch_device can.
+ *
+ * Arena rules, weaker than the other device entries' -- the READ CONTRACT:
+ *  - a part may start at any byte and have any length;
+ *  - the kernel reads only address-aligned 16-byte granules that contain at least
+ *    one byte of a non-empty part, and nothing else of the arena (a part's
+ *    neighbours inside its first and last granule are read and ignored);
+ *  - d_arena itself must be 16-byte aligned (checked here: MSHA_ERR_INVALID_ARG), so
+ *    that granules of offsets are granules of addresses;
+ *  - MSHA_DEVICE_ARENA_SLACK readable bytes must follow the last part.
+ * The host cannot see the device arrays. An action whose part range decreases
+ * (begin[i+1] < begin[i]; or spans 2^32 parts or more) gets an all-zero digest, never a wrong one, and raises a
+ * bit of its own in the device error word: msha_device_status() then returns
+ * MSHA_ERR_INVALID_ARG ("... action_part_begin decreases ...") and clears it. Part
+ * offsets and lengths are trusted, as the offsets of the other device entries are.
+ */
+#define MSHA_HAS_PARTS_DEVICE 1
+int msha_hash_actions_device(msha_ctx* ctx, const uint8_t* d_arena,
+                             const uint64_t* d_part_off, const uint64_t* d_part_len,
+                             const uint64_t* d_action_part_begin, const uint32_t* d_order,
+                             uint64_t n_actions, uint8_t* d_out, void* stream);
+/* Counters of msha_hash_actions_device (msha_stats keeps its size). */
+typedef struct {
+  uint64_t calls;         /* calls that enqueued their launch */
+  uint64_t actions;       /* digests they produce */
+  uint64_t launches;      /* k_digest_parts launches */
+  uint64_t last_lanes;    /* lanes of the last launch */
+  double last_kernel_ms;  /* its kernel time by HIP events, measured only under MSHA_PARTS_TIMING=1
+                             (the call then waits for the kernel; never while `stream` is being
+                             captured); otherwise 0 and the call stays enqueue-only */
+} msha_parts_stats;
+int msha_get_parts_stats(const msha_ctx* ctx, msha_parts_stats* out);
 
 /*
  * Host-only helpers (no GPU needed).

@@ -118,6 +118,16 @@ class MshaStreamsStats(ctypes.Structure):
     ]
 
 
+class MshaPartsStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", ctypes.c_uint64),
+        ("actions", ctypes.c_uint64),
+        ("launches", ctypes.c_uint64),
+        ("last_lanes", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
 _setp = ctypes.c_void_p
 
 # name -> (restype, argtypes)
@@ -174,6 +184,10 @@ SIGNATURES = {
     "msha_finish_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                           ctypes.c_void_p]),
+    "msha_hash_actions_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
+    "msha_get_parts_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaPartsStats)]),
 }
 
 _lib = None
@@ -218,7 +232,8 @@ def lib() -> ctypes.CDLL:
 # The files msha_build_id()'s src hash covers, in the Makefile's order (SRCS).
 _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mirsha.cpp",
               os.path.join("..", "..", "include", "mirsha.h"),
-              "stream_kernels.hip", "stream_pack.hpp", "ctx_access.hpp", "streams.cpp")
+              "stream_kernels.hip", "stream_pack.hpp", "ctx_access.hpp", "streams.cpp",
+              "parts_gather.hpp", "parts_kernels.hip", "parts.cpp")
 
 
 def source_id() -> str:

@@ -7,6 +7,8 @@
 
 #include <mutex>
 
+#include "../../include/mirsha.h"
+
 struct msha_ctx;
 
 namespace msha {
@@ -26,5 +28,7 @@ std::mutex& ctx_mutex(const msha_ctx* ctx);
 int ctx_first_device(msha_ctx* ctx, CtxDevice* out);
 // Sets the context's error text and returns code (msg null: clears the text).
 int ctx_fail(msha_ctx* ctx, int code, const char* msg);
+// The counters of msha_hash_actions_device (parts.cpp). Call with the lock held.
+msha_parts_stats& ctx_parts_stats(msha_ctx* ctx);
 
 }  // namespace msha

@@ -292,6 +292,18 @@ hipError_t launch_stream_rows_set(uint32_t* state, const uint32_t* row, const ui
 hipError_t launch_stream_rows_get(const uint32_t* state, const uint32_t* row, uint32_t* out, uint64_t n,
                                   hipStream_t st);
 
+// Multi-part actions (parts_kernels.hip k_digest_parts, msha_hash_actions_device): lane
+// i hashes action a = order ? order[i] : i, the concatenation of the parts
+// [begin[a], begin[a + 1]) (part j = arena[part_off[j] : part_off[j] + part_len[j]], any
+// start, any length), into out + 32 a. arena is 16-byte aligned; the kernel reads only
+// the aligned 16-byte granules that hold a byte of a non-empty part
+// (parts_gather.hpp). begin[a + 1] < begin[a] sets kErrPartsBegin in *err and zeroes
+// the digest. One launch, no other stream, no host wait: capturable.
+constexpr uint32_t kErrPartsBegin = 4u;  // device error word; 1 and 2 are the alignment and split-timeout flags
+hipError_t launch_digest_parts(const uint8_t* arena, const uint64_t* part_off, const uint64_t* part_len,
+                               const uint64_t* begin, const uint32_t* order, uint64_t n, uint8_t* out,
+                               uint32_t* err, hipStream_t st);
+
 // Clock probe (msha_clock_probe): `workgroups` x 256 lanes compress `blocks`
 // register-resident blocks each; stamps gets (memtime, memrealtime) at start and
 // end per workgroup, 4 words each.

@@ -525,6 +525,7 @@ struct msha_ctx {
   std::vector<Device> devs;
   char err[512] = "";  // last failure on the context (fixed buffer: msha_last_error's pointer stays valid)
   msha_stats stats{};
+  msha_parts_stats parts_stats{};  // msha_hash_actions_device (msha_get_parts_stats)
   // allocations handed out by msha_pinned_alloc: (pointer, mapped bytes), 0 =
   // hipHostMalloc, else an mmap striped over NUMA nodes and hipHostRegister'ed
   std::vector<std::pair<void*, uint64_t>> pinned;
@@ -3164,7 +3165,12 @@ int msha_device_status(msha_ctx* ctx) {
   });
   if (rc != MSHA_OK) return rc;
   if (flag & 2) return fail(ctx, MSHA_ERR_HIP, "split-chain handoff timed out (digests undefined)");
-  if (flag) return fail(ctx, MSHA_ERR_ALIGNMENT, "device arena message start not 16-byte aligned");
+  if (flag & ~msha::kErrPartsBegin)
+    return fail(ctx, MSHA_ERR_ALIGNMENT, "device arena message start not 16-byte aligned");
+  if (flag & msha::kErrPartsBegin)
+    return fail(ctx, MSHA_ERR_INVALID_ARG,
+                "msha_hash_actions_device: action_part_begin decreases (begin[i+1] < begin[i]); "
+                "those digests are zero");
   return MSHA_OK;
 }
 
@@ -3249,7 +3255,7 @@ int msha_pinned_free(msha_ctx* ctx, void* p) {
 
 }  // extern "C"
 
-// ctx_access.hpp: the context as the stream sets (streams.cpp) reach it.
+// ctx_access.hpp: the context as the stream sets (streams.cpp) and the parts entry (parts.cpp) reach it.
 namespace msha {
 
 std::mutex& ctx_mutex(const msha_ctx* ctx) { return ctx->mu; }
@@ -3267,5 +3273,7 @@ int ctx_first_device(msha_ctx* ctx, CtxDevice* out) {
 }
 
 int ctx_fail(msha_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg ? msg : ""); }
+
+msha_parts_stats& ctx_parts_stats(msha_ctx* ctx) { return ctx->parts_stats; }
 
 }  // namespace msha

@@ -242,7 +242,7 @@ class Engine:
         if dev is None:
             dev = self._dev_index = self._device_index()
         sizes = {"off": 8, "length": 8, "begin": 8, "order": 4, "idx": 4, "arena": 1, "table": 1,
-                 "nblocks": 8, "prefix": 8, "state": 4}
+                 "nblocks": 8, "prefix": 8, "state": 4, "part_off": 8, "part_len": 8}
         for name, t in list(tensors.items()) + [("out", out)]:
             if t is None:
                 continue
@@ -306,6 +306,41 @@ class Engine:
                                                  None if prefix is None else prefix.data_ptr(),
                                                  arena.data_ptr(), off.data_ptr(), length.data_ptr(),
                                                  off.numel(), out.data_ptr(), self._stream_ptr(stream)))
+
+    def hash_actions_device(self, arena, part_off, part_len, begin, out, stream=None, order=None) -> None:
+        """msha_hash_actions_device: out[i] = SHA-256 of action i's parts
+        [begin[i], begin[i+1]) back to back, part j = arena[part_off[j] : part_off[j] +
+        part_len[j]] at any byte offset (pack_parts() output, uploaded as is, will do).
+        The arena's base must be 16-byte aligned and MSHA_DEVICE_ARENA_SLACK readable
+        bytes must follow the last part."""
+        n = out.numel() // 32 if hasattr(out, "numel") else 0      # out is n x 32 bytes
+        self._check_device_args(n, out, arena=arena, part_off=part_off, part_len=part_len, begin=begin,
+                                order=order)
+        if out.numel() != 32 * n:
+            raise ValueError(f"out holds {out.numel()} bytes, not a multiple of 32")
+        if begin.numel() != n + 1:
+            raise ValueError(f"begin has {begin.numel()} entries, expected {n + 1} (out holds {n} digests)")
+        if part_len.numel() != part_off.numel():
+            raise ValueError(f"part_len has {part_len.numel()} entries, part_off {part_off.numel()}")
+        if arena.data_ptr() % L.MSHA_DEVICE_ALIGN:
+            raise ValueError(f"arena must start on a {L.MSHA_DEVICE_ALIGN}-byte boundary")
+        if n == 0:
+            return
+        if arena.numel() == 0:          # nothing to read: an empty tensor has no address to pass
+            arena = begin.new_zeros(2)
+        if part_off.numel() == 0:       # every action has zero parts
+            part_off = part_len = begin.new_zeros(2)
+        self._check(self._lib.msha_hash_actions_device(self._ctx, arena.data_ptr(), part_off.data_ptr(),
+                                                       part_len.data_ptr(), begin.data_ptr(),
+                                                       None if order is None else order.data_ptr(), n,
+                                                       out.data_ptr(), self._stream_ptr(stream)))
+
+    def parts_stats(self) -> dict:
+        """msha_get_parts_stats: calls, actions and launches of hash_actions_device, the
+        last launch's lanes and (under MSHA_PARTS_TIMING=1) its kernel time."""
+        s = L.MshaPartsStats()
+        self._check(self._lib.msha_get_parts_stats(self._ctx, ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in L.MshaPartsStats._fields_}
 
     def clock_probe(self, blocks_per_lane: int = 48) -> dict:
         """msha_clock_probe: the clock the first GPU holds under the hash

@@ -153,6 +153,54 @@ def epoch_change_pool(count: int = 100, seed: int = SEED ^ 0x5, n_nodes: int = 1
     return pool
 
 
+def epoch_change_parts_pool(count: int = 100, seed: int = SEED ^ 0x5, n_nodes: int = 100, ci: int = 500,
+                            max_set: int = 1000) -> list[list[bytes]]:
+    """epoch_change_pool()'s payloads in parts form, as epochChangeHashData yields them
+    (8-byte big-endian fields, checkpoint values, 32-byte digests): the join of entry c
+    is epoch_change_pool()[c]. For msha_hash_actions_device, which takes the parts."""
+    from .encoding import Checkpoint, EpochChange, SetEntry, epoch_change_hash_data
+    rng = np.random.Generator(np.random.PCG64(seed))
+    pool = []
+    for c in range(count):      # the draws of epoch_change_pool, in its order
+        cps = [Checkpoint(seq_no=ci * (j + 1), value=rng.bytes(332)) for j in range(2)]
+        npq = rng.integers(0, max_set + 1, size=2)
+        p = [SetEntry(epoch=int(rng.integers(0, 8)), seq_no=int(s), digest=rng.bytes(32))
+             for s in range(int(npq[0]))]
+        q = [SetEntry(epoch=int(rng.integers(0, 8)), seq_no=int(s), digest=rng.bytes(32))
+             for s in range(int(npq[1]))]
+        pool.append(epoch_change_hash_data(EpochChange(new_epoch=c + 1, checkpoints=cps, p_set=p, q_set=q)))
+    return pool
+
+
+def scatter_parts(actions, slack: int = 64):
+    """(arena, part_off, part_len, action_part_begin) with the parts scattered the way a
+    caller holding an EpochChange in HBM has them: the 8-byte fields packed back to back
+    in one region, everything else (digests, checkpoint values) back to back in another
+    (16-byte aligned), so an action's consecutive parts alternate between the regions
+    and the fields sit at every multiple of 8. `slack` readable bytes follow."""
+    fields = [p for a in actions for p in a if len(p) == 8]
+    rest = [p for a in actions for p in a if len(p) != 8]
+    rest_base = _round16(8 * len(fields))
+    arena = np.zeros(rest_base + sum(len(p) for p in rest) + slack, dtype=np.uint8)
+    arena[:8 * len(fields)] = np.frombuffer(b"".join(fields), dtype=np.uint8)
+    arena[rest_base:arena.size - slack] = np.frombuffer(b"".join(rest), dtype=np.uint8)
+    n_parts = len(fields) + len(rest)
+    off = np.zeros(n_parts, dtype=np.uint64)
+    ln = np.zeros(n_parts, dtype=np.uint64)
+    begin = np.zeros(len(actions) + 1, dtype=np.uint64)
+    j, f, r = 0, 0, rest_base
+    for i, a in enumerate(actions):
+        for p in a:
+            ln[j] = len(p)
+            if len(p) == 8:
+                off[j], f = f, f + 8
+            else:
+                off[j], r = r, r + len(p)
+            j += 1
+        begin[i + 1] = j
+    return arena, off, ln, begin
+
+
 def c5_storm(n: int = 1 << 23, first: int = 0, pool: Optional[list] = None) -> Workload:
     """Mixed actions (see module docstring). Action kinds are drawn per index
     from the global stream, so ranks can build disjoint slices independently."""
