@@ -343,7 +343,9 @@ int msha_streams_reset(msha_streams* set, const uint64_t* id, uint64_t k);
 int msha_streams_length(const msha_streams* set, const uint64_t* id, uint64_t k, uint64_t* out);
 /* MarshalBinary / UnmarshalBinary of the streams id[j] (id NULL: all, k == n):
  * k x MSHA_STREAM_STATE_BYTES bytes. Import ignores buffer bytes past length % 64
- * and rejects a wrong magic (MSHA_ERR_INVALID_ARG, no stream changed). */
+ * and rejects a wrong magic (MSHA_ERR_INVALID_ARG, no stream changed). An id
+ * repeated in one import is sequential UnmarshalBinary: the last entry wins for
+ * state, buffer and length alike. */
 int msha_streams_export(msha_streams* set, const uint64_t* id, uint64_t k, uint8_t* out);
 int msha_streams_import(msha_streams* set, const uint64_t* id, uint64_t k, const uint8_t* in);
 typedef struct {

@@ -10,6 +10,7 @@
 #include <exception>
 #include <mutex>
 #include <new>
+#include <numeric>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -397,13 +398,31 @@ int msha_streams_import(msha_streams* s, const uint64_t* id, uint64_t k, const u
     if (std::memcmp(in + MSHA_STREAM_STATE_BYTES * j, kMagic, 4) != 0)
       return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "not an exported SHA-256 state (magic)");
   return run(s, true, [&] {
-    std::vector<uint32_t> vals(8 * k);
-    for (uint64_t j = 0; j < k; ++j)
-      for (int w = 0; w < 8; ++w) vals[8 * j + w] = be32(in + MSHA_STREAM_STATE_BYTES * j + 4 + 4 * w);
-    set_rows(s, id, k, vals.data());
-    for (uint64_t j = 0; j < k; ++j) {
-      const uint64_t r = id_at(id, j);
-      const uint8_t* p = in + MSHA_STREAM_STATE_BYTES * j;
+    // Sequential UnmarshalBinary: of the entries that name one stream the last wins,
+    // for state, buffer and length alike. Only that entry goes to the device: two
+    // rows for one stream in one k_stream_rows_set launch would be stored by two
+    // lanes in no order. `last`: the entries that take effect, in call order.
+    std::vector<uint64_t> last(k);
+    std::iota(last.begin(), last.end(), uint64_t(0));
+    if (id) {
+      std::vector<uint64_t> ord(last);
+      std::stable_sort(ord.begin(), ord.end(), [&](uint64_t a, uint64_t b) { return id[a] < id[b]; });
+      last.clear();
+      for (uint64_t a = 0; a < k; ++a)
+        if (a + 1 == k || id[ord[a + 1]] != id[ord[a]]) last.push_back(ord[a]);
+      std::sort(last.begin(), last.end());
+    }
+    const uint64_t m = last.size();
+    std::vector<uint64_t> ids(m);
+    std::vector<uint32_t> vals(8 * m);
+    for (uint64_t j = 0; j < m; ++j) {
+      ids[j] = id_at(id, last[j]);
+      for (int w = 0; w < 8; ++w) vals[8 * j + w] = be32(in + MSHA_STREAM_STATE_BYTES * last[j] + 4 + 4 * w);
+    }
+    set_rows(s, m ? ids.data() : nullptr, m, vals.data());
+    for (uint64_t j = 0; j < m; ++j) {
+      const uint64_t r = ids[j];
+      const uint8_t* p = in + MSHA_STREAM_STATE_BYTES * last[j];
       const uint64_t L = (uint64_t)be32(p + 100) << 32 | be32(p + 104);
       s->length[r] = L;
       std::memset(&s->tail[64 * r], 0, 64);
