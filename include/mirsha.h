@@ -436,6 +436,84 @@ typedef struct {
 int msha_get_parts_stats(const msha_ctx* ctx, msha_parts_stats* out);
 
 /*
+ * Multi-part actions through part LISTS, planned and folded on the GPU (ABI 10,
+ * additive: MSHA_HAS_PARTS_PLANNED tells a build that has it). One more level of
+ * indirection than msha_hash_actions_device, actions -> lists -> parts:
+ *   list l           = parts [d_list_part_begin[l], d_list_part_begin[l+1])
+ *   action i         hashes list d_action_list[i]  (d_action_list NULL: list i, and
+ *                    n_actions must equal n_lists)
+ *   d_out[32*i ...]  = SHA-256(the list's parts back to back)
+ * Parts, the arena and d_out are as in msha_hash_actions_device, under its READ
+ * CONTRACT (any byte offset, 16-byte granules, a 16-byte aligned d_arena,
+ * MSHA_DEVICE_ARENA_SLACK readable bytes after the last part). d_list_part_begin has
+ * n_lists + 1 entries; n_lists and n_actions are each below 2^32 - 1.
+ *
+ * FOLDING comes with the indirection: two actions are the same message exactly when
+ * they name the same list (an integer compare: no contents are hashed or compared to
+ * find that out). Every list named at least once is hashed exactly once, however many
+ * actions name it. A list no action names is not hashed, and neither its entry of
+ * d_list_part_begin nor its parts are read. `flags` is reserved (MSHA_PARTS_FOLD names
+ * what is implied anyway); any other bit is MSHA_ERR_INVALID_ARG.
+ *
+ * ORDER: the lanes are the named lists, ordered on the GPU inside the call by
+ * descending block-count class -- the exact block count below 4,096 blocks, powers of
+ * two from there up, as msha_digest_batch_device_planned orders its lanes -- so the
+ * lanes of a wave finish together. The order inside a class is unspecified.
+ *
+ * ERRORS the host cannot see are reported by msha_device_status(), once:
+ *  - d_action_list[i] >= n_lists: action i gets an all-zero digest and bit 8 of the
+ *    device error word is raised: MSHA_ERR_INVALID_ARG ("... action_list out of range
+ *    ...");
+ *  - a list whose part range decreases (or spans 2^32 parts or more): every action
+ *    naming it gets an all-zero digest, and the bit msha_hash_actions_device raises for
+ *    it (4) is raised: MSHA_ERR_INVALID_ARG ("... action_part_begin decreases ...").
+ * Checked on the host (MSHA_ERR_INVALID_ARG): null pointers, d_arena's alignment,
+ * unknown flags, the two counts' bound, n_actions != n_lists without d_action_list.
+ * n_actions == 0 returns MSHA_OK and launches nothing.
+ *
+ * ONE STREAM, capturable: the kernels (init, mark, measure, scan, scatter, hash, fill)
+ * all go on `stream` (NULL: the context's own); there is no memset, no library stream
+ * and no host wait. The workspace (class keys, counters, the order, a used flag per list, and
+ * with d_action_list the lists' digest table: 6 to 39 bytes a list) belongs to the
+ * context and grows by hipMalloc only while `stream` is NOT being captured; growing
+ * waits for the previous call. On a capturing stream with too small a workspace (or a
+ * context that has made no device call yet) the call fails with MSHA_ERR_INVALID_ARG
+ * and says to make one call of that size outside the capture first. Outside capture a
+ * call is ordered after the previous planned-parts call of the context through a
+ * library event, so calls on two streams do not race on the workspace. A captured call
+ * holds the workspace's addresses: replaying it concurrently with another planned-parts
+ * call on the same context is the caller's to order, and a later call that grows the
+ * workspace invalidates it.
+ */
+#define MSHA_HAS_PARTS_PLANNED 1
+enum { MSHA_PARTS_FOLD = 1u };
+int msha_hash_actions_device_planned(msha_ctx* ctx, const uint8_t* d_arena,
+                                     const uint64_t* d_part_off, const uint64_t* d_part_len,
+                                     const uint64_t* d_list_part_begin, uint64_t n_lists,
+                                     const uint32_t* d_action_list, uint64_t n_actions,
+                                     uint32_t flags, uint8_t* d_out, void* stream);
+/* Counters of msha_hash_actions_device_planned (msha_stats and msha_parts_stats are
+ * untouched by it). */
+typedef struct {
+  uint64_t calls;          /* calls that enqueued their launches */
+  uint64_t actions;        /* digests they produce */
+  uint64_t lists;          /* lists they were given */
+  uint64_t last_lanes;     /* the last call's distinct lists hashed ... */
+  uint64_t last_blocks;    /* ... and the 64-byte blocks compressed for them; both read back, and */
+  uint64_t launches_plan;  /* init, mark, measure, scan and scatter launches */
+  uint64_t launches_hash;  /* k_digest_parts_planned launches */
+  uint64_t launches_fill;  /* k_parts_fill launches (calls with d_action_list) */
+  double last_kernel_ms;   /* the call's kernels timed by HIP events, only under MSHA_PARTS_TIMING=1
+                              (read at each call; the call then waits for its kernels; never while
+                              `stream` is being captured); otherwise these three are 0 */
+} msha_parts_plan_stats;
+int msha_get_parts_plan_stats(const msha_ctx* ctx, msha_parts_plan_stats* out);
+/* Diagnostic, synchronous: waits for the device, then copies the last call's lane order
+ * (list indices, position 0 first) into order[0 .. min(cap, *lanes)) and its lane count
+ * into *lanes. order may be NULL when cap is 0. */
+int msha_parts_plan_read_order(msha_ctx* ctx, uint32_t* order, uint64_t cap, uint64_t* lanes);
+
+/*
  * Host-only helpers (no GPU needed).
  * msha_blocks_for_len: number of 64-byte compressions for an L-byte message,
  *   floor(L/64) + (L%64 < 56 ? 1 : 2)  (FIPS 180-4 5.1.1 padding).

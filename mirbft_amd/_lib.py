@@ -32,6 +32,7 @@ MSHA_KERNEL_AUTO = 0
 MSHA_KERNEL_LANE = 1
 MSHA_KERNEL_COOP = 2
 MSHA_STREAM_STATE_BYTES = 108
+MSHA_PARTS_FOLD = 1
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -128,6 +129,20 @@ class MshaPartsStats(ctypes.Structure):
     ]
 
 
+class MshaPartsPlanStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", ctypes.c_uint64),
+        ("actions", ctypes.c_uint64),
+        ("lists", ctypes.c_uint64),
+        ("last_lanes", ctypes.c_uint64),
+        ("last_blocks", ctypes.c_uint64),
+        ("launches_plan", ctypes.c_uint64),
+        ("launches_hash", ctypes.c_uint64),
+        ("launches_fill", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
 _setp = ctypes.c_void_p
 
 # name -> (restype, argtypes)
@@ -188,6 +203,12 @@ SIGNATURES = {
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                                 ctypes.c_void_p, ctypes.c_void_p]),
     "msha_get_parts_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaPartsStats)]),
+    "msha_hash_actions_device_planned": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                        ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
+                                                        ctypes.c_void_p]),
+    "msha_get_parts_plan_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaPartsPlanStats)]),
+    "msha_parts_plan_read_order": (ctypes.c_int, [_ctxp, _u32p, ctypes.c_uint64, _u64p]),
 }
 
 _lib = None
@@ -233,7 +254,8 @@ def lib() -> ctypes.CDLL:
 _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mirsha.cpp",
               os.path.join("..", "..", "include", "mirsha.h"),
               "stream_kernels.hip", "stream_pack.hpp", "ctx_access.hpp", "streams.cpp",
-              "parts_gather.hpp", "parts_kernels.hip", "parts.cpp")
+              "parts_gather.hpp", "parts_kernels.hip", "parts.cpp",
+              "parts_digest.hpp", "parts_plan.hpp", "parts_plan.hip", "parts_plan.cpp")
 
 
 def source_id() -> str:

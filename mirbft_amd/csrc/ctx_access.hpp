@@ -31,4 +31,31 @@ int ctx_fail(msha_ctx* ctx, int code, const char* msg);
 // The counters of msha_hash_actions_device (parts.cpp). Call with the lock held.
 msha_parts_stats& ctx_parts_stats(msha_ctx* ctx);
 
+// What msha_hash_actions_device_planned (parts_plan.cpp) keeps in the context: its
+// device workspace (one allocation, on the first device), the event that orders a call
+// after the previous one's use of it, and its counters. Freed by msha_ctx_destroy.
+struct PartsPlanState {
+  void* ws = nullptr;
+  uint64_t ws_bytes = 0;
+  hipEvent_t last = nullptr;  // recorded after each call outside capture
+  uint64_t last_lists = 0;    // n_lists of the last call (msha_parts_plan_read_order)
+  bool ran = false;           // some call has filled the workspace
+  msha_parts_plan_stats stats{};
+  void release() {
+    if (last) {
+      (void)hipEventSynchronize(last);
+      (void)hipEventDestroy(last);
+    }
+    if (ws) (void)hipFree(ws);
+    ws = nullptr;
+    last = nullptr;
+    ws_bytes = 0;
+  }
+};
+// Call with the lock held.
+PartsPlanState& ctx_parts_plan(msha_ctx* ctx);
+// Has a device call already allocated the first device's error word? Until then
+// ctx_first_device allocates, which a capturing stream does not allow.
+bool ctx_first_device_ready(const msha_ctx* ctx);
+
 }  // namespace msha

@@ -304,6 +304,39 @@ hipError_t launch_digest_parts(const uint8_t* arena, const uint64_t* part_off, c
                                const uint64_t* begin, const uint32_t* order, uint64_t n, uint8_t* out,
                                uint32_t* err, hipStream_t st);
 
+// Multi-part actions through part lists, planned on the GPU (parts_plan.hip,
+// msha_hash_actions_device_planned). List l owns the parts [begin[l], begin[l + 1]);
+// action i names list action_list[i] (null: action i is list i, n_actions == n_lists).
+// The lanes are the lists some action names, each hashed once, in descending
+// block-count class (parts_plan.hpp); the workspace arrays are the caller's, device
+// memory, and everything runs on one stream with no host wait: capturable.
+constexpr uint32_t kErrPartsList = 8u;  // device error word: an action_list entry >= n_lists
+struct PartsPlanArgs {
+  const uint8_t* arena = nullptr;
+  const uint64_t* part_off = nullptr;
+  const uint64_t* part_len = nullptr;
+  const uint64_t* begin = nullptr;        // n_lists + 1
+  uint64_t n_lists = 0;
+  const uint32_t* action_list = nullptr;  // n_actions, or null
+  uint64_t n_actions = 0;
+  uint8_t* used = nullptr;    // (with action_list) n_lists bytes (rounded up to words) -> 1: some action
+                              // names the list
+  uint16_t* key16 = nullptr;  // n_lists: out, the list's class key, parts_plan::kNoKey when unused
+  uint32_t* cnt = nullptr;    // info + 16: parts_plan::kKeys counters -> bucket starts -> bucket ends
+  uint32_t* info = nullptr;   // 16 words: [0] lanes, [2..3] the lanes' block sum (64-bit)
+  uint32_t* order = nullptr;  // n_lists: position -> list, kNoLane past the lanes
+  uint8_t* table = nullptr;   // (with action_list) 32 n_lists bytes: list l's digest
+  uint8_t* out = nullptr;     // 32 n_actions bytes
+  uint32_t* err = nullptr;
+  uint32_t wave_sum_parts = 0;  // lists of this many parts or more are summed by their wave
+};
+// init (resets the workspace), mark (with action_list), measure, scan, scatter; *launches = how many kernels that was.
+hipError_t launch_parts_plan(const PartsPlanArgs& a, hipStream_t st, uint32_t* launches);
+// k_digest_parts_planned over a.order: digests to a.table (with action_list) or a.out.
+hipError_t launch_digest_parts_planned(const PartsPlanArgs& a, hipStream_t st);
+// (with action_list) out[i] = table[action_list[i]], zeros for an entry out of range.
+hipError_t launch_parts_fill(const PartsPlanArgs& a, hipStream_t st);
+
 // Clock probe (msha_clock_probe): `workgroups` x 256 lanes compress `blocks`
 // register-resident blocks each; stamps gets (memtime, memrealtime) at start and
 // end per workgroup, 4 words each.

@@ -526,6 +526,7 @@ struct msha_ctx {
   char err[512] = "";  // last failure on the context (fixed buffer: msha_last_error's pointer stays valid)
   msha_stats stats{};
   msha_parts_stats parts_stats{};  // msha_hash_actions_device (msha_get_parts_stats)
+  msha::PartsPlanState parts_plan;  // msha_hash_actions_device_planned (parts_plan.cpp)
   // allocations handed out by msha_pinned_alloc: (pointer, mapped bytes), 0 =
   // hipHostMalloc, else an mmap striped over NUMA nodes and hipHostRegister'ed
   std::vector<std::pair<void*, uint64_t>> pinned;
@@ -2592,6 +2593,7 @@ void msha_ctx_destroy(msha_ctx* ctx) {
     (void)hipSetDevice(d.id);
     for (hipStream_t st : {d.stream, d.copy_stream, d.d2h_stream})
       if (st) (void)hipStreamSynchronize(st);
+    if (&d == &ctx->devs[0]) ctx->parts_plan.release();  // its workspace lives on the first device
     d.release();
   }
   for (const auto& a : ctx->pinned) pinned_release(a);
@@ -3165,11 +3167,16 @@ int msha_device_status(msha_ctx* ctx) {
   });
   if (rc != MSHA_OK) return rc;
   if (flag & 2) return fail(ctx, MSHA_ERR_HIP, "split-chain handoff timed out (digests undefined)");
-  if (flag & ~msha::kErrPartsBegin)
+  if (flag & ~(msha::kErrPartsBegin | msha::kErrPartsList))
     return fail(ctx, MSHA_ERR_ALIGNMENT, "device arena message start not 16-byte aligned");
   if (flag & msha::kErrPartsBegin)
     return fail(ctx, MSHA_ERR_INVALID_ARG,
-                "msha_hash_actions_device: action_part_begin decreases (begin[i+1] < begin[i]); "
+                std::string("msha_hash_actions_device: action_part_begin decreases (begin[i+1] < begin[i]); "
+                            "those digests are zero") +
+                    ((flag & msha::kErrPartsList) ? "; and action_list out of range (an entry >= n_lists)" : ""));
+  if (flag & msha::kErrPartsList)
+    return fail(ctx, MSHA_ERR_INVALID_ARG,
+                "msha_hash_actions_device_planned: action_list out of range (an entry >= n_lists); "
                 "those digests are zero");
   return MSHA_OK;
 }
@@ -3275,5 +3282,9 @@ int ctx_first_device(msha_ctx* ctx, CtxDevice* out) {
 int ctx_fail(msha_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg ? msg : ""); }
 
 msha_parts_stats& ctx_parts_stats(msha_ctx* ctx) { return ctx->parts_stats; }
+
+PartsPlanState& ctx_parts_plan(msha_ctx* ctx) { return ctx->parts_plan; }
+
+bool ctx_first_device_ready(const msha_ctx* ctx) { return !ctx->devs.empty() && ctx->devs[0].err.p != nullptr; }
 
 }  // namespace msha

@@ -242,7 +242,8 @@ class Engine:
         if dev is None:
             dev = self._dev_index = self._device_index()
         sizes = {"off": 8, "length": 8, "begin": 8, "order": 4, "idx": 4, "arena": 1, "table": 1,
-                 "nblocks": 8, "prefix": 8, "state": 4, "part_off": 8, "part_len": 8}
+                 "nblocks": 8, "prefix": 8, "state": 4, "part_off": 8, "part_len": 8, "list_begin": 8,
+                 "action_list": 4}
         for name, t in list(tensors.items()) + [("out", out)]:
             if t is None:
                 continue
@@ -253,7 +254,7 @@ class Engine:
             want = 1 if name == "out" else sizes[name]
             if t.element_size() != want or t.is_floating_point():
                 raise ValueError(f"{name} must hold {want}-byte integers (got {t.dtype})")
-        for name in ("off", "length", "order", "nblocks", "prefix"):
+        for name in ("off", "length", "order", "nblocks", "prefix", "action_list"):
             t = tensors.get(name)
             if t is not None and t.numel() != n:
                 raise ValueError(f"{name} has {t.numel()} entries, expected {n}")
@@ -341,6 +342,58 @@ class Engine:
         s = L.MshaPartsStats()
         self._check(self._lib.msha_get_parts_stats(self._ctx, ctypes.byref(s)))
         return {name: getattr(s, name) for name, _ in L.MshaPartsStats._fields_}
+
+    def hash_actions_device_planned(self, arena, part_off, part_len, list_begin, out, action_list=None,
+                                    stream=None) -> None:
+        """msha_hash_actions_device_planned: list l owns the parts [list_begin[l],
+        list_begin[l+1]); out[i] = SHA-256 of the parts of list action_list[i] back to
+        back (action_list None: of list i). Every list some action names is hashed
+        once, the others not at all, and the lanes run in descending block-count
+        class, planned on the GPU inside the call. Arena rules as hash_actions_device."""
+        n = out.numel() // 32 if hasattr(out, "numel") else 0      # out is n x 32 bytes
+        self._check_device_args(n, out, arena=arena, part_off=part_off, part_len=part_len,
+                                list_begin=list_begin, action_list=action_list)
+        if out.numel() != 32 * n:
+            raise ValueError(f"out holds {out.numel()} bytes, not a multiple of 32")
+        n_lists = list_begin.numel() - 1
+        if n_lists < 0:
+            raise ValueError("list_begin must have at least one entry")
+        if action_list is None and n_lists != n:
+            raise ValueError(f"list_begin has {list_begin.numel()} entries, expected {n + 1} (out holds {n} digests "
+                             "and there is no action_list)")
+        if part_len.numel() != part_off.numel():
+            raise ValueError(f"part_len has {part_len.numel()} entries, part_off {part_off.numel()}")
+        if arena.data_ptr() % L.MSHA_DEVICE_ALIGN:
+            raise ValueError(f"arena must start on a {L.MSHA_DEVICE_ALIGN}-byte boundary")
+        if n == 0:
+            return
+        if arena.numel() == 0:          # nothing to read: an empty tensor has no address to pass
+            arena = list_begin.new_zeros(2)
+        if part_off.numel() == 0:       # every list has zero parts
+            part_off = part_len = list_begin.new_zeros(2)
+        self._check(self._lib.msha_hash_actions_device_planned(
+            self._ctx, arena.data_ptr(), part_off.data_ptr(), part_len.data_ptr(), list_begin.data_ptr(), n_lists,
+            None if action_list is None else action_list.data_ptr(), n, 0, out.data_ptr(),
+            self._stream_ptr(stream)))
+
+    def parts_plan_stats(self) -> dict:
+        """msha_get_parts_plan_stats: calls, actions, lists and launches of
+        hash_actions_device_planned and, under MSHA_PARTS_TIMING=1, the last call's
+        lanes (distinct lists hashed), blocks compressed and kernel time."""
+        s = L.MshaPartsPlanStats()
+        self._check(self._lib.msha_get_parts_plan_stats(self._ctx, ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in L.MshaPartsPlanStats._fields_}
+
+    def parts_plan_order(self) -> np.ndarray:
+        """msha_parts_plan_read_order: the last hash_actions_device_planned call's lane
+        order (list indices, first lane first). Waits for the device; a diagnostic."""
+        lanes = ctypes.c_uint64(0)
+        self._check(self._lib.msha_parts_plan_read_order(self._ctx, None, 0, ctypes.byref(lanes)))
+        order = np.empty(lanes.value, dtype=np.uint32)
+        if lanes.value:
+            self._check(self._lib.msha_parts_plan_read_order(self._ctx, _p(order, ctypes.c_uint32), order.size,
+                                                             ctypes.byref(lanes)))
+        return order[:lanes.value]
 
     def clock_probe(self, blocks_per_lane: int = 48) -> dict:
         """msha_clock_probe: the clock the first GPU holds under the hash
