@@ -308,14 +308,27 @@ struct Device {
 // Consecutive launches use different flag arrays of a ring and unique epochs,
 // so a launch never reads another launch's flags.
 constexpr uint64_t kSplitRing = 16;
+// d's flag ring, zeroed before this returns (msha_ctx_create makes it, while d's
+// stream is still empty). Every context counts its epochs from 1 and hipMalloc
+// hands back an earlier context's ring as it was left, with that context's
+// hand-offs of the same epochs in it, so the zeros must be there before a
+// launch's first poll. A hipMemset does not promise that: it may return before
+// the fill has run, on the null stream, which the streams here (non-blocking)
+// are not ordered with. A segment that found such a flag went ahead of the one
+// before it and took the digest slot's old bytes for the chain's state: wrong
+// digests for the surplus lanes of the launch, and no error bit.
+void ensure_split_flags(Device& d) {
+  if (d.split_flags) return;
+  const uint64_t bytes = kSplitRing * (uint64_t)d.cus * 2 * sizeof(uint64_t);
+  HIPCHK(hipMalloc(&d.split_flags, bytes));
+  HIPCHK(hipMemsetAsync(d.split_flags, 0, bytes, d.stream));
+  HIPCHK(hipStreamSynchronize(d.stream));
+}
 const msha::SplitPlan* split_for(Device& d, uint64_t n, int policy, msha::SplitPlan& sp,
                                  int cap = msha::kMaxSegmentsArena) {
   if (!msha::plan_split(n, d.cus, policy, &sp, cap)) return nullptr;
   const uint64_t per = (uint64_t)d.cus * 2;  // plan_split: chains <= SIMDs / 2
-  if (!d.split_flags) {
-    HIPCHK(hipMalloc(&d.split_flags, kSplitRing * per * sizeof(uint64_t)));
-    HIPCHK(hipMemset(d.split_flags, 0, kSplitRing * per * sizeof(uint64_t)));
-  }
+  ensure_split_flags(d);
   sp.epoch = ++d.split_epoch;
   sp.flags = d.split_flags + (sp.epoch % kSplitRing) * per;
   return &sp;
@@ -2567,6 +2580,7 @@ int msha_ctx_create_err(uint32_t device_mask, msha_ctx** out, char* errbuf, uint
         HIPCHK(hipEventCreateWithFlags(&d.slot_free[0], hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&d.slot_free[1], hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&d.chunk_in, hipEventDisableTiming));
+        ensure_split_flags(d);
         d.st.device = i;
         d.index = (uint32_t)ctx->devs.size();
         ctx->devs.push_back(std::move(d));

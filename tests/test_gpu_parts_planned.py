@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import parts_matrix
+import parts_plan_matrix
 from mirbft_amd import MshaError, pack_parts
 from mirbft_amd import _lib as L
 
@@ -126,6 +127,7 @@ def test_mixed_classes_in_one_call(engine):
     assert _bad_rows(got, _want(lists)) == []
     order = engine.parts_plan_order()
     assert sorted(order.tolist()) == list(range(len(lists)))
+    parts_plan_matrix.check_plan(order, parts_plan_matrix.plan_model(ln, begin))
     blocks = np.array([_blocks(sum(len(p) for p in a)) for a in lists])
     along = blocks[order]
     assert (np.diff(along) <= 0).all(), along.tolist()
@@ -160,6 +162,7 @@ def test_folding_hashes_each_named_list_once(engine, actions_golden, monkeypatch
     assert st["last_kernel_ms"] > 0
     order = engine.parts_plan_order()
     assert sorted(order.tolist()) == named and order[0] == 22
+    parts_plan_matrix.check_plan(order, parts_plan_matrix.plan_model(ln, begin, al), lanes=st["last_lanes"])
     # without the variable nothing is read back
     got = _run(engine, arena, off, ln, begin, action_list=al)
     st = engine.parts_plan_stats()
