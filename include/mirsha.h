@@ -514,6 +514,87 @@ int msha_get_parts_plan_stats(const msha_ctx* ctx, msha_parts_plan_stats* out);
 int msha_parts_plan_read_order(msha_ctx* ctx, uint32_t* order, uint64_t cap, uint64_t* lanes);
 
 /*
+ * Part lists flattened on the GPU (ABI 10, additive: MSHA_HAS_PARTS_CONCAT tells a
+ * build that has it). The parts kernels above walk a list on one lane; every other
+ * device entry wants contiguous, MSHA_DEVICE_ALIGN-aligned messages. This entry turns
+ * selected lists into such messages without a host round trip, so that a caller can
+ * hand its long lists (an EpochChange: thousands of parts) to msha_digest_batch_device
+ * and leave the short ones on msha_hash_actions_device_planned.
+ *
+ * MESSAGES. Message k, for k in [0, n_select), is list s = d_select[k]; with d_select
+ * NULL message k is list k and n_select must equal n_lists. List s owns the parts
+ * [d_list_part_begin[s], d_list_part_begin[s+1]) (n_lists + 1 entries), and part j is
+ * d_arena[d_part_off[j] : d_part_off[j] + d_part_len[j]], as in
+ * msha_hash_actions_device_planned. An id may repeat in d_select: each repeat is
+ * another copy, a message of its own.
+ *
+ * LAYOUT. d_msg_len[k] is the sum of the list's part lengths, d_msg_off[0] = 0 and
+ * d_msg_off[k+1] = d_msg_off[k] + round16(d_msg_len[k]): every start is
+ * MSHA_DEVICE_ALIGN-aligned, messages come in k order, and there are no gaps beyond
+ * the pad. d_msg_off and d_msg_len have n_select entries each.
+ *
+ * BYTES WRITTEN. d_dst[off[k] : off[k] + len[k]] holds the list's parts back to back,
+ * and the pad up to round16(len[k]) is written as zeros. No other byte of d_dst is
+ * written.
+ *
+ * FIT. Message k fits iff off[k] + round16(len[k]) + MSHA_DEVICE_ARENA_SLACK <=
+ * dst_bytes: with that slack whatever the digest entries read past a message stays
+ * inside d_dst, so (d_dst, d_msg_off, d_msg_len) can go to msha_digest_batch_device as
+ * they are.
+ *
+ * NEVER AN UNSAFE LAYOUT. Three kinds of message are not written: one that does not
+ * fit; one whose d_select[k] >= n_lists; one whose list's part range decreases or spans
+ * 2^32 parts or more. Such a message gets d_msg_off[k] = d_msg_len[k] = 0 (the empty
+ * message at d_dst's start), so nothing downstream reads outside d_dst. An invalid list
+ * (the last two kinds) counts as length 0 in the running offset. A message that does
+ * not fit counts with its length, so once one message does not fit, none after it does
+ * either: all of them are refused, and every message before them is exact. Each of the
+ * three raises bit 16 of the device error word: msha_device_status() then returns
+ * MSHA_ERR_INVALID_ARG with a text that names msha_concat_lists_device and the three
+ * causes, once, and clears it. Set together with an older bit, that bit's code and
+ * text are reported unchanged and this clause is appended to them.
+ *
+ * READ CONTRACT: the one of msha_hash_actions_device. Only address-aligned 16-byte
+ * granules that hold a byte of a non-empty part of a selected, valid list are read (a
+ * refused list's parts are not read at all); d_list_part_begin[s] and [s+1] of lists
+ * nobody selects are not read. Part offsets and lengths are trusted. d_dst must not
+ * overlap the arena or any of the arrays: that is the caller's error and is not
+ * detected.
+ *
+ * Checked on the host (MSHA_ERR_INVALID_ARG, each with a text): null pointers; d_arena
+ * or d_dst not MSHA_DEVICE_ALIGN-aligned; n_lists or n_select at or above 2^32 - 1;
+ * n_select != n_lists without d_select. n_select == 0 returns MSHA_OK and launches
+ * nothing.
+ *
+ * ONE STREAM, capturable: three kernels (measure, scan, copy) go on `stream` (NULL: the
+ * context's own). There is no memset, no library stream, no host wait and no workspace
+ * of the context's -- between the first two kernels d_msg_off carries a flag -- so the
+ * call captures into a HIP graph as a linear chain of three kernel nodes. The one
+ * allocation is the context's error word on its first device call: on a capturing
+ * stream a context that has made no device call yet fails with MSHA_ERR_INVALID_ARG
+ * and says to make one call of this size outside the capture first.
+ */
+#define MSHA_HAS_PARTS_CONCAT 1
+int msha_concat_lists_device(msha_ctx* ctx, const uint8_t* d_arena,
+                             const uint64_t* d_part_off, const uint64_t* d_part_len,
+                             const uint64_t* d_list_part_begin, uint64_t n_lists,
+                             const uint32_t* d_select, uint64_t n_select,
+                             uint8_t* d_dst, uint64_t dst_bytes,
+                             uint64_t* d_msg_off, uint64_t* d_msg_len, void* stream);
+/* Counters of msha_concat_lists_device (msha_stats, msha_parts_stats and
+ * msha_parts_plan_stats are untouched by it). */
+typedef struct {
+  uint64_t calls;         /* calls that enqueued their launches */
+  uint64_t lists;         /* messages they were asked for (n_select) */
+  uint64_t launches;      /* kernel launches: three a call */
+  uint64_t last_bytes;    /* the last call's last valid message's off + round16(len), read back, and */
+  double last_kernel_ms;  /* its kernels timed by HIP events, only under MSHA_PARTS_TIMING=1 (read at
+                             each call; the call then waits for its kernels; never while `stream` is
+                             being captured); otherwise both are 0 */
+} msha_concat_stats;
+int msha_get_concat_stats(const msha_ctx* ctx, msha_concat_stats* out);
+
+/*
  * Host-only helpers (no GPU needed).
  * msha_blocks_for_len: number of 64-byte compressions for an L-byte message,
  *   floor(L/64) + (L%64 < 56 ? 1 : 2)  (FIPS 180-4 5.1.1 padding).

@@ -33,6 +33,7 @@ MSHA_KERNEL_LANE = 1
 MSHA_KERNEL_COOP = 2
 MSHA_STREAM_STATE_BYTES = 108
 MSHA_PARTS_FOLD = 1
+MSHA_HAS_PARTS_CONCAT = 1
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -143,6 +144,16 @@ class MshaPartsPlanStats(ctypes.Structure):
     ]
 
 
+class MshaConcatStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", ctypes.c_uint64),
+        ("lists", ctypes.c_uint64),
+        ("launches", ctypes.c_uint64),
+        ("last_bytes", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
 _setp = ctypes.c_void_p
 
 # name -> (restype, argtypes)
@@ -209,6 +220,11 @@ SIGNATURES = {
                                                         ctypes.c_void_p]),
     "msha_get_parts_plan_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaPartsPlanStats)]),
     "msha_parts_plan_read_order": (ctypes.c_int, [_ctxp, _u32p, ctypes.c_uint64, _u64p]),
+    "msha_concat_lists_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "msha_get_concat_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaConcatStats)]),
 }
 
 _lib = None
@@ -255,7 +271,8 @@ _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mi
               os.path.join("..", "..", "include", "mirsha.h"),
               "stream_kernels.hip", "stream_pack.hpp", "ctx_access.hpp", "streams.cpp",
               "parts_gather.hpp", "parts_kernels.hip", "parts.cpp",
-              "parts_digest.hpp", "parts_plan.hpp", "parts_plan.hip", "parts_plan.cpp")
+              "parts_digest.hpp", "parts_plan.hpp", "parts_plan.hip", "parts_plan.cpp",
+              "parts_concat.hpp", "parts_concat.hip", "parts_concat.cpp")
 
 
 def source_id() -> str:

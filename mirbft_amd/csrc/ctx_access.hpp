@@ -30,6 +30,8 @@ int ctx_first_device(msha_ctx* ctx, CtxDevice* out);
 int ctx_fail(msha_ctx* ctx, int code, const char* msg);
 // The counters of msha_hash_actions_device (parts.cpp). Call with the lock held.
 msha_parts_stats& ctx_parts_stats(msha_ctx* ctx);
+// The counters of msha_concat_lists_device (parts_concat.cpp). Call with the lock held.
+msha_concat_stats& ctx_concat_stats(msha_ctx* ctx);
 
 // What msha_hash_actions_device_planned (parts_plan.cpp) keeps in the context: its
 // device workspace (one allocation, on the first device), the event that orders a call

@@ -337,6 +337,31 @@ hipError_t launch_digest_parts_planned(const PartsPlanArgs& a, hipStream_t st);
 // (with action_list) out[i] = table[action_list[i]], zeros for an entry out of range.
 hipError_t launch_parts_fill(const PartsPlanArgs& a, hipStream_t st);
 
+// Part lists flattened into contiguous messages (parts_concat.hip,
+// msha_concat_lists_device). Message k is list select[k] (null: list k); its parts go
+// back to back to dst + msg_off[k], msg_off a running sum of round16(msg_len). Three
+// kernels on one stream, no workspace and no host wait: capturable.
+constexpr uint32_t kErrPartsConcat = 16u;  // device error word: a message of msha_concat_lists_device was refused
+struct ConcatArgs {
+  const uint8_t* arena = nullptr;
+  const uint64_t* part_off = nullptr;
+  const uint64_t* part_len = nullptr;
+  const uint64_t* begin = nullptr;   // n_lists + 1
+  uint64_t n_lists = 0;
+  const uint32_t* select = nullptr;  // n_select, or null
+  uint64_t n_select = 0;
+  uint8_t* dst = nullptr;
+  uint64_t dst_bytes = 0;
+  uint64_t* msg_off = nullptr;       // n_select: between measure and scan, 1 marks an invalid message
+  uint64_t* msg_len = nullptr;       // n_select
+  uint32_t* err = nullptr;
+  uint32_t wave_sum_parts = 0;       // lists of this many parts or more are summed by their wave
+};
+// k_concat_measure, k_concat_scan, k_concat_copy, in that order; one launch each.
+hipError_t launch_concat_measure(const ConcatArgs& a, hipStream_t st);
+hipError_t launch_concat_scan(const ConcatArgs& a, hipStream_t st);
+hipError_t launch_concat_copy(const ConcatArgs& a, hipStream_t st);
+
 // Clock probe (msha_clock_probe): `workgroups` x 256 lanes compress `blocks`
 // register-resident blocks each; stamps gets (memtime, memrealtime) at start and
 // end per workgroup, 4 words each.

@@ -540,6 +540,7 @@ struct msha_ctx {
   msha_stats stats{};
   msha_parts_stats parts_stats{};  // msha_hash_actions_device (msha_get_parts_stats)
   msha::PartsPlanState parts_plan;  // msha_hash_actions_device_planned (parts_plan.cpp)
+  msha_concat_stats concat_stats{};  // msha_concat_lists_device (parts_concat.cpp)
   // allocations handed out by msha_pinned_alloc: (pointer, mapped bytes), 0 =
   // hipHostMalloc, else an mmap striped over NUMA nodes and hipHostRegister'ed
   std::vector<std::pair<void*, uint64_t>> pinned;
@@ -3180,18 +3181,27 @@ int msha_device_status(msha_ctx* ctx) {
     HIPCHK(hipMemset(d.err.p, 0, 4));
   });
   if (rc != MSHA_OK) return rc;
-  if (flag & 2) return fail(ctx, MSHA_ERR_HIP, "split-chain handoff timed out (digests undefined)");
-  if (flag & ~(msha::kErrPartsBegin | msha::kErrPartsList))
-    return fail(ctx, MSHA_ERR_ALIGNMENT, "device arena message start not 16-byte aligned");
+  // bit 16 (msha_concat_lists_device): alone it is the whole text; with an older bit that
+  // bit's code and text stay as they are and this clause follows them
+  const char* const concat_text =
+      "msha_concat_lists_device: a message was refused (it does not fit d_dst, its d_select entry is >= n_lists, "
+      "or its list's part range decreases or spans 2^32 parts or more); its d_msg_off and d_msg_len are zero";
+  const std::string concat = (flag & msha::kErrPartsConcat) ? std::string("; and ") + concat_text : std::string();
+  if (flag & 2) return fail(ctx, MSHA_ERR_HIP, "split-chain handoff timed out (digests undefined)" + concat);
+  if (flag & ~(msha::kErrPartsBegin | msha::kErrPartsList | msha::kErrPartsConcat))
+    return fail(ctx, MSHA_ERR_ALIGNMENT, "device arena message start not 16-byte aligned" + concat);
   if (flag & msha::kErrPartsBegin)
     return fail(ctx, MSHA_ERR_INVALID_ARG,
                 std::string("msha_hash_actions_device: action_part_begin decreases (begin[i+1] < begin[i]); "
                             "those digests are zero") +
-                    ((flag & msha::kErrPartsList) ? "; and action_list out of range (an entry >= n_lists)" : ""));
+                    ((flag & msha::kErrPartsList) ? "; and action_list out of range (an entry >= n_lists)" : "") +
+                    concat);
   if (flag & msha::kErrPartsList)
     return fail(ctx, MSHA_ERR_INVALID_ARG,
                 "msha_hash_actions_device_planned: action_list out of range (an entry >= n_lists); "
-                "those digests are zero");
+                "those digests are zero" +
+                    concat);
+  if (flag & msha::kErrPartsConcat) return fail(ctx, MSHA_ERR_INVALID_ARG, concat_text);
   return MSHA_OK;
 }
 
@@ -3296,6 +3306,8 @@ int ctx_first_device(msha_ctx* ctx, CtxDevice* out) {
 int ctx_fail(msha_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg ? msg : ""); }
 
 msha_parts_stats& ctx_parts_stats(msha_ctx* ctx) { return ctx->parts_stats; }
+
+msha_concat_stats& ctx_concat_stats(msha_ctx* ctx) { return ctx->concat_stats; }
 
 PartsPlanState& ctx_parts_plan(msha_ctx* ctx) { return ctx->parts_plan; }
 

@@ -243,7 +243,7 @@ class Engine:
             dev = self._dev_index = self._device_index()
         sizes = {"off": 8, "length": 8, "begin": 8, "order": 4, "idx": 4, "arena": 1, "table": 1,
                  "nblocks": 8, "prefix": 8, "state": 4, "part_off": 8, "part_len": 8, "list_begin": 8,
-                 "action_list": 4}
+                 "action_list": 4, "dst": 1, "msg_off": 8, "msg_len": 8, "select": 4}
         for name, t in list(tensors.items()) + [("out", out)]:
             if t is None:
                 continue
@@ -394,6 +394,51 @@ class Engine:
             self._check(self._lib.msha_parts_plan_read_order(self._ctx, _p(order, ctypes.c_uint32), order.size,
                                                              ctypes.byref(lanes)))
         return order[:lanes.value]
+
+    def concat_lists_device(self, arena, part_off, part_len, list_begin, dst, msg_off, msg_len, select=None,
+                            stream=None) -> None:
+        """msha_concat_lists_device: message k is list select[k] (select None: list k),
+        its parts [list_begin[s], list_begin[s+1]) written back to back to dst at
+        msg_off[k], msg_len[k] bytes, every start 16-byte aligned and the pad zeroed.
+        (dst, msg_off, msg_len) then go to digest_batch_device as they are. A message
+        that does not fit dst (with MSHA_DEVICE_ARENA_SLACK after it) or names an
+        invalid list gets msg_off = msg_len = 0 and device_status() reports it. Arena
+        rules as hash_actions_device; dst must start on a 16-byte boundary."""
+        self._check_device_args(0, None, arena=arena, part_off=part_off, part_len=part_len,
+                                list_begin=list_begin, dst=dst, msg_off=msg_off, msg_len=msg_len, select=select)
+        n_lists = list_begin.numel() - 1
+        if n_lists < 0:
+            raise ValueError("list_begin must have at least one entry")
+        n = n_lists if select is None else select.numel()
+        if msg_off.numel() != n or msg_len.numel() != n:
+            raise ValueError(f"msg_off and msg_len have {msg_off.numel()} and {msg_len.numel()} entries, "
+                             f"expected {n}")
+        if part_len.numel() != part_off.numel():
+            raise ValueError(f"part_len has {part_len.numel()} entries, part_off {part_off.numel()}")
+        if arena.data_ptr() % L.MSHA_DEVICE_ALIGN:
+            raise ValueError(f"arena must start on a {L.MSHA_DEVICE_ALIGN}-byte boundary")
+        if dst.data_ptr() % L.MSHA_DEVICE_ALIGN:
+            raise ValueError(f"dst must start on a {L.MSHA_DEVICE_ALIGN}-byte boundary")
+        if n == 0:
+            return
+        if arena.numel() == 0:          # nothing to read: an empty tensor has no address to pass
+            arena = list_begin.new_zeros(2)
+        if part_off.numel() == 0:       # every list has zero parts
+            part_off = part_len = list_begin.new_zeros(2)
+        dst_bytes = dst.numel()
+        if dst_bytes == 0:              # everything is refused; still a valid address
+            dst = list_begin.new_zeros(2)
+        self._check(self._lib.msha_concat_lists_device(
+            self._ctx, arena.data_ptr(), part_off.data_ptr(), part_len.data_ptr(), list_begin.data_ptr(), n_lists,
+            None if select is None else select.data_ptr(), n, dst.data_ptr(), dst_bytes,
+            msg_off.data_ptr(), msg_len.data_ptr(), self._stream_ptr(stream)))
+
+    def concat_stats(self) -> dict:
+        """msha_get_concat_stats: calls, lists and launches of concat_lists_device and,
+        under MSHA_PARTS_TIMING=1, the last call's bytes laid out and kernel time."""
+        s = L.MshaConcatStats()
+        self._check(self._lib.msha_get_concat_stats(self._ctx, ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in L.MshaConcatStats._fields_}
 
     def clock_probe(self, blocks_per_lane: int = 48) -> dict:
         """msha_clock_probe: the clock the first GPU holds under the hash
