@@ -384,6 +384,99 @@ int msha_finish_device(msha_ctx* ctx, const uint32_t* d_state, const uint64_t* d
                        uint8_t* d_out, void* stream);
 
 /*
+ * Device stream sets: the stream sets above with everything in device memory (ABI 10,
+ * additive: MSHA_HAS_STREAMS_DEVICE tells a build that has them). NodeState.Apply
+ * (pkg/testengine/recorder.go:333-359) writes each committed request digest into
+ * ActiveHash, and Snap (recorder.go:288-300) takes Sum(nil), starts a new hash and
+ * writes the sum into it. When those digests are produced in HBM
+ * (msha_digest_batch_device), a host set costs a copy down, a repack, a copy up and a
+ * wait per call; msha_absorb_device / msha_finish_device take whole 16-byte aligned
+ * blocks only and leave the partial-block bookkeeping to the host. Here a stream's
+ * chaining state, its 64-byte buffer (bytes past length % 64 always zero) and its
+ * 64-bit length all live on the context's first device, allocated once in create.
+ *
+ * Write, Sum, Snap and Reset are DEVICE CALLS: every pointer is device memory of the
+ * context's first device, `stream` NULL means the context's own stream, and the call
+ * returns after enqueueing exactly one kernel launch -- no memset, no library stream,
+ * no event wait, no allocation -- so it captures into a HIP graph as one kernel node
+ * (a replayed write appends again). n_rows == 0 returns MSHA_OK and launches nothing.
+ * Ordering between calls on different HIP streams is the caller's. A set must be
+ * destroyed before its context; calls on it take the context's lock.
+ *
+ * Rows. Row r of a call, r in [0, n_rows), is stream s = d_row ? d_row[r] : r (d_row
+ * NULL: n_rows must equal n, checked here). A stream may be named AT MOST ONCE per
+ * call, the rule of the host sets' row kernels; a repeat is NOT detected: that stream
+ * alone is left in an unspecified state, no other stream is affected and nothing is
+ * read or written outside the set's memory. A stream's chunks of one call go into one
+ * row's part list, which is what the CSR d_row_part_begin (n_rows + 1 entries) is for.
+ *
+ * Write (hash.Hash.Write; recorder.go:348): row r appends the parts
+ * [d_row_part_begin[r], d_row_part_begin[r+1]) back to back,
+ *   part j = d_arena[d_part_off[j] : d_part_off[j] + d_part_len[j]].
+ * The arena rules are the READ CONTRACT of msha_hash_actions_device below: a part may
+ * start at any byte and have any length; only address-aligned 16-byte granules that
+ * hold a byte of a non-empty part are read; d_arena must be 16-byte aligned (checked
+ * here: MSHA_ERR_INVALID_ARG); MSHA_DEVICE_ARENA_SLACK readable bytes must follow the
+ * last part. Part offsets are below 2^63 (bit 63 marks the stream's own buffer inside
+ * the kernel; an offset that carries it reads that buffer, never other memory). Empty
+ * parts and zero-part rows contribute nothing; a row that appends nothing stores
+ * nothing.
+ *
+ * Checked on the host (MSHA_ERR_INVALID_ARG with a text): null pointers, d_arena's
+ * alignment, n_rows >= 2^32 - 1, d_row NULL with n_rows != n, an import with a wrong
+ * magic. Reported by msha_device_status(), once, for what the host cannot see:
+ *  - d_row[r] >= n: no stream is touched, Sum and Snap zero that d_out row, and a bit
+ *    of its own (32) is raised in the device error word: MSHA_ERR_INVALID_ARG
+ *    ("msha_dstreams_*: row out of range ..."), appended to an older bit's text when
+ *    one is raised too;
+ *  - a row whose part range decreases (or spans 2^32 parts or more): the stream is
+ *    unchanged, and the bit and text of msha_hash_actions_device's decreasing
+ *    action_part_begin are raised.
+ */
+#define MSHA_HAS_STREAMS_DEVICE 1
+typedef struct msha_dstreams msha_dstreams;
+/* n streams in New() state (recorder.go:420, Hasher.New()); n in [1, 2^32 - 1). */
+int msha_dstreams_create(msha_ctx* ctx, uint64_t n, msha_dstreams** out);
+void msha_dstreams_destroy(msha_dstreams* set);
+int msha_dstreams_write_device(msha_dstreams* set, const uint8_t* d_arena,
+                               const uint64_t* d_part_off, const uint64_t* d_part_len,
+                               const uint64_t* d_row_part_begin, const uint32_t* d_row,
+                               uint64_t n_rows, void* stream);
+/* Sum(nil) (recorder.go:298): d_out[32 r] = SHA-256 of everything written to row r's
+ * stream; no stream changes. */
+int msha_dstreams_sum_device(msha_dstreams* set, const uint32_t* d_row, uint64_t n_rows,
+                             uint8_t* d_out, void* stream);
+/* Snap (recorder.go:298-300): d_out[32 r] = Sum(nil); then the stream is New()
+ * followed by Write(that sum): 32 bytes buffered, length 32. */
+int msha_dstreams_snap_device(msha_dstreams* set, const uint32_t* d_row, uint64_t n_rows,
+                              uint8_t* d_out, void* stream);
+/* Reset (hash.Hash.Reset): the rows' streams return to New(). */
+int msha_dstreams_reset_device(msha_dstreams* set, const uint32_t* d_row, uint64_t n_rows,
+                               void* stream);
+/* Synchronous, host memory: these wait for the device (everything enqueued on it so
+ * far), then read or replace whole streams; id NULL: all n streams, k == n; an id >= n
+ * is MSHA_ERR_INVALID_ARG. Export and import use the MSHA_STREAM_STATE_BYTES layout of
+ * msha_streams_export, so a state moves freely between a host set and a device set.
+ * Import ignores buffer bytes past length % 64 (they are stored as zeros) and rejects
+ * a wrong magic with no stream changed; of the entries naming one stream the last
+ * wins, as in msha_streams_import. */
+int msha_dstreams_length(msha_dstreams* set, const uint64_t* id, uint64_t k, uint64_t* out);
+int msha_dstreams_export(msha_dstreams* set, const uint64_t* id, uint64_t k, uint8_t* out);
+int msha_dstreams_import(msha_dstreams* set, const uint64_t* id, uint64_t k, const uint8_t* in);
+typedef struct {
+  uint64_t writes;        /* device calls that enqueued their launch, by kind */
+  uint64_t sums;
+  uint64_t snaps;
+  uint64_t resets;
+  uint64_t launches;      /* kernel launches of those calls: one each */
+  uint64_t last_rows;     /* rows of the last one */
+  double last_kernel_ms;  /* its kernel time by HIP events, measured only under MSHA_PARTS_TIMING=1
+                             (the call then waits for the kernel; never while `stream` is being
+                             captured); otherwise 0 and the call stays enqueue-only */
+} msha_dstreams_stats;
+int msha_dstreams_get_stats(const msha_dstreams* set, msha_dstreams_stats* out);
+
+/*
  * ProcessHashActions from HBM (serial.go:180-198), the device-resident form of
  * msha_hash_actions (ABI 10, additive: MSHA_HAS_PARTS_DEVICE tells a build that has
  * it). An action's Data is a list of byte slices hashed back to back; an

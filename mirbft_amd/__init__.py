@@ -9,11 +9,12 @@ from .processor import (Action, ActionHashRequest, ActionList, EventHashResult, 
                         HashOrigin, HashOriginBatch, HashOriginEpochChange, HashOriginVerifyBatch,
                         ProcessHashActions, ProcessorError, action_hash, checkpoint_hashes)
 from .streams import StreamSet
+from .streams_device import DeviceStreamSet
 
 __all__ = [
     "Engine", "MshaError", "blocks_for_len", "device_count", "pack_parts", "partition_by_blocks",
     "Action", "ActionHashRequest", "ActionList", "EventHashResult", "EventList", "GPUHasher",
     "HashOrigin", "HashOriginBatch", "HashOriginEpochChange", "HashOriginVerifyBatch",
     "ProcessHashActions", "ProcessorError", "action_hash", "checkpoint_hashes",
-    "StreamSet",
+    "StreamSet", "DeviceStreamSet",
 ]

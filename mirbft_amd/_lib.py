@@ -34,6 +34,7 @@ MSHA_KERNEL_COOP = 2
 MSHA_STREAM_STATE_BYTES = 108
 MSHA_PARTS_FOLD = 1
 MSHA_HAS_PARTS_CONCAT = 1
+MSHA_HAS_STREAMS_DEVICE = 1
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -154,6 +155,18 @@ class MshaConcatStats(ctypes.Structure):
     ]
 
 
+class MshaDstreamsStats(ctypes.Structure):
+    _fields_ = [
+        ("writes", ctypes.c_uint64),
+        ("sums", ctypes.c_uint64),
+        ("snaps", ctypes.c_uint64),
+        ("resets", ctypes.c_uint64),
+        ("launches", ctypes.c_uint64),
+        ("last_rows", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
 _setp = ctypes.c_void_p
 
 # name -> (restype, argtypes)
@@ -225,6 +238,20 @@ SIGNATURES = {
                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "msha_get_concat_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaConcatStats)]),
+    "msha_dstreams_create": (ctypes.c_int, [_ctxp, ctypes.c_uint64, ctypes.POINTER(_setp)]),
+    "msha_dstreams_destroy": (None, [_setp]),
+    "msha_dstreams_write_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                  ctypes.c_void_p]),
+    "msha_dstreams_sum_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
+    "msha_dstreams_snap_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
+    "msha_dstreams_reset_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "msha_dstreams_length": (ctypes.c_int, [_setp, _u64p, ctypes.c_uint64, _u64p]),
+    "msha_dstreams_export": (ctypes.c_int, [_setp, _u64p, ctypes.c_uint64, _u8p]),
+    "msha_dstreams_import": (ctypes.c_int, [_setp, _u64p, ctypes.c_uint64, _u8p]),
+    "msha_dstreams_get_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaDstreamsStats)]),
 }
 
 _lib = None
@@ -272,6 +299,7 @@ _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mi
               "stream_kernels.hip", "stream_pack.hpp", "ctx_access.hpp", "streams.cpp",
               "parts_gather.hpp", "parts_kernels.hip", "parts.cpp",
               "parts_digest.hpp", "parts_plan.hpp", "parts_plan.hip", "parts_plan.cpp",
+              "stream_device.hpp", "stream_device.hip", "stream_device.cpp",
               "parts_concat.hpp", "parts_concat.hip", "parts_concat.cpp")
 
 

@@ -292,6 +292,39 @@ hipError_t launch_stream_rows_set(uint32_t* state, const uint32_t* row, const ui
 hipError_t launch_stream_rows_get(const uint32_t* state, const uint32_t* row, uint32_t* out, uint64_t n,
                                   hipStream_t st);
 
+// Device stream sets (stream_device.hip, msha_dstreams_*): a stream is row s of three
+// device arrays -- state + 8 s (eight host-order words), tail + 64 s (the buffered
+// length % 64 bytes, zero past them) and length + s. Lane i works on stream
+// s = row ? row[i] : i (a launch names a stream at most once); s >= n sets kErrStreamRow
+// in *err and touches no stream (finish zeroes the digest). One launch each, no other
+// stream, no host wait: capturable.
+//  write:  stream s appends the parts [begin[i], begin[i + 1]) of the arena (rules of
+//          launch_digest_parts below); a decreasing range sets kErrPartsBegin and
+//          leaves the stream as it was.
+//  finish: out + 32 i = the digest of everything written to s; snap: the stream then
+//          is New() followed by Write(that digest).
+//  reset:  the streams return to New().
+//  rows_get / rows_set: whole streams to and from packed rows of 26 dwords (state,
+//          tail, length low and high); ids checked by the host, id null: row i.
+constexpr uint32_t kErrStreamRow = 32u;  // device error word: a row of msha_dstreams_* names a stream >= n
+struct DstreamRows {
+  uint32_t* state = nullptr;
+  uint8_t* tail = nullptr;
+  uint64_t* length = nullptr;
+  uint64_t n = 0;
+};
+hipError_t launch_dstream_write(const DstreamRows& r, const uint8_t* arena, const uint64_t* part_off,
+                                const uint64_t* part_len, const uint64_t* begin, const uint32_t* row,
+                                uint64_t n_rows, uint32_t* err, hipStream_t st);
+hipError_t launch_dstream_finish(const DstreamRows& r, const uint32_t* row, uint64_t n_rows, uint8_t* out, bool snap,
+                                 uint32_t* err, hipStream_t st);
+hipError_t launch_dstream_reset(const DstreamRows& r, const uint32_t* row, uint64_t n_rows, uint32_t* err,
+                                hipStream_t st);
+hipError_t launch_dstream_rows_get(const DstreamRows& r, const uint32_t* id, uint64_t k, uint32_t* packed,
+                                   hipStream_t st);
+hipError_t launch_dstream_rows_set(const DstreamRows& r, const uint32_t* id, uint64_t k, const uint32_t* packed,
+                                   hipStream_t st);
+
 // Multi-part actions (parts_kernels.hip k_digest_parts, msha_hash_actions_device): lane
 // i hashes action a = order ? order[i] : i, the concatenation of the parts
 // [begin[a], begin[a + 1]) (part j = arena[part_off[j] : part_off[j] + part_len[j]], any

@@ -3186,9 +3186,13 @@ int msha_device_status(msha_ctx* ctx) {
   const char* const concat_text =
       "msha_concat_lists_device: a message was refused (it does not fit d_dst, its d_select entry is >= n_lists, "
       "or its list's part range decreases or spans 2^32 parts or more); its d_msg_off and d_msg_len are zero";
-  const std::string concat = (flag & msha::kErrPartsConcat) ? std::string("; and ") + concat_text : std::string();
+  // bit 32 (msha_dstreams_*): the same rule, after the concat clause when both are raised
+  const char* const row_text =
+      "msha_dstreams_*: row out of range (a d_row entry >= n); no stream was touched and those digests are zero";
+  const std::string concat = ((flag & msha::kErrPartsConcat) ? std::string("; and ") + concat_text : std::string()) +
+                             ((flag & msha::kErrStreamRow) ? std::string("; and ") + row_text : std::string());
   if (flag & 2) return fail(ctx, MSHA_ERR_HIP, "split-chain handoff timed out (digests undefined)" + concat);
-  if (flag & ~(msha::kErrPartsBegin | msha::kErrPartsList | msha::kErrPartsConcat))
+  if (flag & ~(msha::kErrPartsBegin | msha::kErrPartsList | msha::kErrPartsConcat | msha::kErrStreamRow))
     return fail(ctx, MSHA_ERR_ALIGNMENT, "device arena message start not 16-byte aligned" + concat);
   if (flag & msha::kErrPartsBegin)
     return fail(ctx, MSHA_ERR_INVALID_ARG,
@@ -3201,7 +3205,10 @@ int msha_device_status(msha_ctx* ctx) {
                 "msha_hash_actions_device_planned: action_list out of range (an entry >= n_lists); "
                 "those digests are zero" +
                     concat);
-  if (flag & msha::kErrPartsConcat) return fail(ctx, MSHA_ERR_INVALID_ARG, concat_text);
+  if (flag & msha::kErrPartsConcat)
+    return fail(ctx, MSHA_ERR_INVALID_ARG,
+                std::string(concat_text) + ((flag & msha::kErrStreamRow) ? std::string("; and ") + row_text : std::string()));
+  if (flag & msha::kErrStreamRow) return fail(ctx, MSHA_ERR_INVALID_ARG, row_text);
   return MSHA_OK;
 }
 

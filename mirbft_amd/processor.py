@@ -194,6 +194,13 @@ class GPUHasher:
         from .streams import StreamSet
         return StreamSet(self.engine, n, staging_bytes)
 
+    def new_device_streams(self, n: int):
+        """n resumable hash.Hash streams kept entirely in device memory
+        (DeviceStreamSet): written from parts that already sit in HBM, summed and
+        snapped there, one launch a call with no host wait."""
+        from .streams_device import DeviceStreamSet
+        return DeviceStreamSet(self.engine, n)
+
     def hash_batch(self, actions: Sequence[Sequence[bytes]]) -> List[bytes]:
         return self.engine.hash_actions(actions)
 
