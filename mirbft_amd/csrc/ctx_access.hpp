@@ -1,6 +1,7 @@
 // What a translation unit outside mirsha.cpp may reach of a context (msha_ctx is
-// defined there): its lock, its first device, its error text. Defined in
-// mirsha.cpp; used by the stream sets (streams.cpp).
+// defined there): its lock, its first device, its error text and what the device
+// entries keep in it. Defined at the end of mirsha.cpp; used, through host_call.hpp, by
+// streams.cpp, parts.cpp, parts_plan.cpp, parts_concat.cpp and stream_device.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,10 +23,9 @@ struct CtxDevice {
 
 // The lock every call on the context takes.
 std::mutex& ctx_mutex(const msha_ctx* ctx);
-// The context's first device, made current, with its error word allocated. Returns
-// MSHA_OK, or an MSHA_ERR_* code with the context's error text set. Call with the
-// lock held.
-int ctx_first_device(msha_ctx* ctx, CtxDevice* out);
+// The context's first device, made current, with its error word allocated. Throws
+// (host_call.hpp MshaError): call inside guard(), with the lock held.
+CtxDevice ctx_first_device(msha_ctx* ctx);
 // Sets the context's error text and returns code (msg null: clears the text).
 int ctx_fail(msha_ctx* ctx, int code, const char* msg);
 // The counters of msha_hash_actions_device (parts.cpp). Call with the lock held.

@@ -33,21 +33,11 @@
 #include "../../include/mirsha.h"
 #include "kernels.hpp"
 #include "ctx_access.hpp"
+#include "host_call.hpp"
 
 namespace {
 
-struct MshaError : std::runtime_error {
-  int code;
-  MshaError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess)                                                                    \
-      throw MshaError(e_ == hipErrorOutOfMemory ? MSHA_ERR_OUT_OF_MEMORY : MSHA_ERR_HIP,     \
-                      std::string(#expr) + ": " + hipGetErrorString(e_));                    \
-  } while (0)
+using msha::MshaError;
 
 // Reason of the most recent failed context creation in the process
 // (msha_last_error(NULL)). A fixed, always NUL-terminated buffer written under a
@@ -579,9 +569,11 @@ unsigned host_threads_total(const msha_ctx* ctx) {
   return std::min(want, hw);
 }
 
+// A call on the context: msha::guard() (host_call.hpp) with the context's wide pool
+// installed for the call's whole-batch phases.
 template <class F>
 int guarded(msha_ctx* ctx, F&& f) {
-  struct PoolScope {  // the context's wide pool for this call's whole-batch phases
+  struct PoolScope {
     WorkerPool* prev = tl_pool;
     explicit PoolScope(msha_ctx* c) {
       if (c && !c->devs.empty()) {
@@ -592,20 +584,10 @@ int guarded(msha_ctx* ctx, F&& f) {
     }
     ~PoolScope() { tl_pool = prev; }
   };
-  try {
+  return msha::guard(ctx, [&] {
     PoolScope scope(ctx);
     f();
-    if (ctx) ctx->err[0] = '\0';
-    return MSHA_OK;
-  } catch (const MshaError& e) {
-    return fail(ctx, e.code, e.what());
-  } catch (const std::bad_alloc&) {
-    return fail(ctx, MSHA_ERR_OUT_OF_MEMORY, "host allocation failed");
-  } catch (const std::exception& e) {
-    return fail(ctx, MSHA_ERR_HIP, e.what());
-  } catch (...) {
-    return fail(ctx, MSHA_ERR_HIP, "unknown error");
-  }
+  });
 }
 
 // Split [0, n) into nearly equal contiguous pieces and run f(lo, hi) on the
@@ -3293,21 +3275,22 @@ int msha_pinned_free(msha_ctx* ctx, void* p) {
 
 }  // extern "C"
 
-// ctx_access.hpp: the context as the stream sets (streams.cpp) and the parts entry (parts.cpp) reach it.
+// ctx_access.hpp: the context as the translation units beside this one reach it (the
+// stream sets, the parts entries, the device stream sets).
 namespace msha {
 
 std::mutex& ctx_mutex(const msha_ctx* ctx) { return ctx->mu; }
 
-int ctx_first_device(msha_ctx* ctx, CtxDevice* out) {
-  return guarded(ctx, [&] {
-    hipStream_t st;
-    device_prologue(ctx, nullptr, &st);
-    const Device& d = ctx->devs[0];
-    out->id = d.id;
-    out->cus = d.cus;
-    out->stream = st;
-    out->err = d.err.as<uint32_t>();
-  });
+CtxDevice ctx_first_device(msha_ctx* ctx) {
+  hipStream_t st;
+  device_prologue(ctx, nullptr, &st);
+  const Device& d = ctx->devs[0];
+  CtxDevice out;
+  out.id = d.id;
+  out.cus = d.cus;
+  out.stream = st;
+  out.err = d.err.as<uint32_t>();
+  return out;
 }
 
 int ctx_fail(msha_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg ? msg : ""); }

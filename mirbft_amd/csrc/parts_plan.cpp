@@ -10,30 +10,12 @@
 #include <string>
 
 #include "../../include/mirsha.h"
-#include "ctx_access.hpp"
-#include "kernels.hpp"
+#include "host_call.hpp"
 #include "parts_plan.hpp"
 
 namespace {
 
 const char* const kEntry = "msha_hash_actions_device_planned";
-
-int hip_fail(msha_ctx* ctx, const char* what, hipError_t e) {
-  return msha::ctx_fail(ctx, e == hipErrorOutOfMemory ? MSHA_ERR_OUT_OF_MEMORY : MSHA_ERR_HIP,
-                        (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-
-int bad_arg(msha_ctx* ctx, const std::string& what) {
-  return msha::ctx_fail(ctx, MSHA_ERR_INVALID_ARG, (std::string(kEntry) + ": " + what).c_str());
-}
-
-struct EventPair {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~EventPair() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
 
 uint64_t round64(uint64_t x) { return (x + 63) & ~uint64_t(63); }
 
@@ -63,117 +45,95 @@ int msha_hash_actions_device_planned(msha_ctx* ctx, const uint8_t* d_arena, cons
                                      uint32_t flags, uint8_t* d_out, void* stream) {
   if (!ctx) return MSHA_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(ctx));
-  if (flags & ~(uint32_t)MSHA_PARTS_FOLD) return bad_arg(ctx, "unknown flags " + std::to_string(flags));
+  if (flags & ~(uint32_t)MSHA_PARTS_FOLD) return msha::bad_arg(ctx, kEntry, "unknown flags " + std::to_string(flags));
   if (n_lists >= 0xffffffffull || n_actions >= 0xffffffffull)
-    return bad_arg(ctx, "n_lists and n_actions must be below 2^32 - 1");
+    return msha::bad_arg(ctx, kEntry, "n_lists and n_actions must be below 2^32 - 1");
   if (!d_action_list && n_actions != n_lists)
-    return bad_arg(ctx, "without d_action_list action i is list i: n_actions (" + std::to_string(n_actions) +
-                            ") must equal n_lists (" + std::to_string(n_lists) + ")");
+    return msha::bad_arg(ctx, kEntry, "without d_action_list action i is list i: n_actions (" +
+                                          std::to_string(n_actions) + ") must equal n_lists (" +
+                                          std::to_string(n_lists) + ")");
   if (n_actions == 0) return MSHA_OK;
   if (!d_arena || !d_part_off || !d_part_len || !d_list_part_begin || !d_out)
     return msha::ctx_fail(ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
   if (reinterpret_cast<uintptr_t>(d_arena) % MSHA_DEVICE_ALIGN)
-    return bad_arg(ctx, "d_arena must be 16-byte aligned");
+    return msha::bad_arg(ctx, kEntry, "d_arena must be 16-byte aligned");
 
-  // a capturing stream allows no allocation: know that before the context's first
-  // device call would make one (the error word) or the workspace would grow
-  hipError_t e;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (stream && (e = hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cap)) != hipSuccess)
-    return hip_fail(ctx, "hipStreamIsCapturing", e);
-  const bool capturing = cap != hipStreamCaptureStatusNone;
-  msha::PartsPlanState& ps = msha::ctx_parts_plan(ctx);
-  const Layout lay(n_lists, d_action_list != nullptr);
-  if (capturing && (!msha::ctx_first_device_ready(ctx) || lay.bytes > ps.ws_bytes))
-    return bad_arg(ctx, "the workspace cannot grow while the stream is being captured: make one call of "
-                        "this size outside the capture first");
+  return msha::guard(ctx, [&] {
+    // a capturing stream allows no allocation: know that before the context's first
+    // device call would make one (the error word) or the workspace would grow
+    const bool capturing = stream && msha::stream_capturing(static_cast<hipStream_t>(stream));
+    msha::PartsPlanState& ps = msha::ctx_parts_plan(ctx);
+    const Layout lay(n_lists, d_action_list != nullptr);
+    if (capturing && (!msha::ctx_first_device_ready(ctx) || lay.bytes > ps.ws_bytes))
+      throw msha::MshaError(MSHA_ERR_INVALID_ARG,
+                            std::string(kEntry) + ": the workspace cannot grow while the stream is being captured: "
+                                                  "make one call of this size outside the capture first");
+    msha::CtxDevice d;
+    const hipStream_t st = msha::device_entry(ctx, kEntry, stream, capturing, &d);
 
-  msha::CtxDevice d;
-  const int rc = msha::ctx_first_device(ctx, &d);
-  if (rc != MSHA_OK) return rc;
-  const hipStream_t st = stream ? static_cast<hipStream_t>(stream) : d.stream;
+    if (lay.bytes > ps.ws_bytes) {
+      // an earlier call may still be using the old buffer
+      if (ps.last) HIPCHK(hipEventSynchronize(ps.last));
+      if (ps.ws) HIPCHK(hipFree(ps.ws));
+      ps.ws = nullptr;
+      ps.ws_bytes = 0;
+      ps.ran = false;
+      const uint64_t want = lay.bytes + lay.bytes / 4;
+      HIPCHK(hipMalloc(&ps.ws, want));
+      ps.ws_bytes = want;
+    }
+    if (!ps.last && !capturing) HIPCHK(hipEventCreateWithFlags(&ps.last, hipEventDisableTiming));
+    // two streams must not race on the workspace: after the previous call's last kernel
+    if (!capturing && ps.ran) HIPCHK(hipStreamWaitEvent(st, ps.last, 0));
 
-  if (lay.bytes > ps.ws_bytes) {
-    // an earlier call may still be using the old buffer
-    if (ps.last && (e = hipEventSynchronize(ps.last)) != hipSuccess) return hip_fail(ctx, "hipEventSynchronize", e);
-    if (ps.ws && (e = hipFree(ps.ws)) != hipSuccess) return hip_fail(ctx, "hipFree", e);
-    ps.ws = nullptr;
-    ps.ws_bytes = 0;
-    ps.ran = false;
-    const uint64_t want = lay.bytes + lay.bytes / 4;
-    if ((e = hipMalloc(&ps.ws, want)) != hipSuccess) return hip_fail(ctx, "hipMalloc (parts plan workspace)", e);
-    ps.ws_bytes = want;
-  }
-  if (!ps.last && !capturing &&
-      (e = hipEventCreateWithFlags(&ps.last, hipEventDisableTiming)) != hipSuccess)
-    return hip_fail(ctx, "hipEventCreate", e);
-  // two streams must not race on the workspace: after the previous call's last kernel
-  if (!capturing && ps.ran && (e = hipStreamWaitEvent(st, ps.last, 0)) != hipSuccess)
-    return hip_fail(ctx, "hipStreamWaitEvent", e);
+    uint8_t* ws = static_cast<uint8_t*>(ps.ws);
+    msha::PartsPlanArgs a;
+    a.arena = d_arena;
+    a.part_off = d_part_off;
+    a.part_len = d_part_len;
+    a.begin = d_list_part_begin;
+    a.n_lists = n_lists;
+    a.action_list = d_action_list;
+    a.n_actions = n_actions;
+    a.info = reinterpret_cast<uint32_t*>(ws);
+    a.cnt = a.info + 16;
+    a.order = reinterpret_cast<uint32_t*>(ws + lay.order);
+    a.key16 = reinterpret_cast<uint16_t*>(ws + lay.key16);
+    a.used = d_action_list ? ws + lay.used : nullptr;
+    a.table = d_action_list ? ws + lay.table : nullptr;
+    a.out = d_out;
+    a.err = d.err;
+    const int t = msha::env_int("MSHA_PARTS_PLAN_WAVE_SUM", (int)msha::parts_plan::kWaveSumParts);
+    a.wave_sum_parts = t < 1 ? 1u : (uint32_t)t;
+    // MSHA_PARTS_PLAN_ONLY=1 (diagnostic, tools/parts_plan_bench.py): stop after the
+    // scatter, so the plan kernels can be timed alone; no digest is written
+    const bool plan_only = msha::env_int("MSHA_PARTS_PLAN_ONLY", 0) == 1;
 
-  // MSHA_PARTS_TIMING=1 (diagnostic): time the kernels with HIP events and read the
-  // lane and block counts back, which makes the call wait; never on a capturing stream
-  const bool timed = !capturing && msha::env_int("MSHA_PARTS_TIMING", 0) == 1;
-  EventPair ev;
-  if (timed) {
-    if ((e = hipEventCreate(&ev.a)) != hipSuccess) return hip_fail(ctx, "hipEventCreate", e);
-    if ((e = hipEventCreate(&ev.b)) != hipSuccess) return hip_fail(ctx, "hipEventCreate", e);
-  }
+    // under MSHA_PARTS_TIMING=1 the lane and block counts are read back too, which makes
+    // the call wait
+    msha::LaunchTimer timer(st, !capturing && msha::LaunchTimer::wanted());
+    uint32_t plan_launches = 0;
+    msha::launch_check(msha::launch_parts_plan(a, st, &plan_launches), "parts plan launch");
+    if (!plan_only) msha::launch_check(msha::launch_digest_parts_planned(a, st), "k_digest_parts_planned launch");
+    if (!plan_only && d_action_list) msha::launch_check(msha::launch_parts_fill(a, st), "k_parts_fill launch");
+    ps.ran = true;
+    ps.last_lists = n_lists;
+    if (!capturing) HIPCHK(hipEventRecord(ps.last, st));
 
-  uint8_t* ws = static_cast<uint8_t*>(ps.ws);
-  msha::PartsPlanArgs a;
-  a.arena = d_arena;
-  a.part_off = d_part_off;
-  a.part_len = d_part_len;
-  a.begin = d_list_part_begin;
-  a.n_lists = n_lists;
-  a.action_list = d_action_list;
-  a.n_actions = n_actions;
-  a.info = reinterpret_cast<uint32_t*>(ws);
-  a.cnt = a.info + 16;
-  a.order = reinterpret_cast<uint32_t*>(ws + lay.order);
-  a.key16 = reinterpret_cast<uint16_t*>(ws + lay.key16);
-  a.used = d_action_list ? ws + lay.used : nullptr;
-  a.table = d_action_list ? ws + lay.table : nullptr;
-  a.out = d_out;
-  a.err = d.err;
-  const int t = msha::env_int("MSHA_PARTS_PLAN_WAVE_SUM", (int)msha::parts_plan::kWaveSumParts);
-  a.wave_sum_parts = t < 1 ? 1u : (uint32_t)t;
-
-  if (timed && (e = hipEventRecord(ev.a, st)) != hipSuccess) return hip_fail(ctx, "hipEventRecord", e);
-  uint32_t plan_launches = 0;
-  if ((e = msha::launch_parts_plan(a, st, &plan_launches)) != hipSuccess) return hip_fail(ctx, "parts plan launch", e);
-  // MSHA_PARTS_PLAN_ONLY=1 (diagnostic, tools/parts_plan_bench.py): stop after the
-  // scatter, so the plan kernels can be timed alone; no digest is written
-  const bool plan_only = msha::env_int("MSHA_PARTS_PLAN_ONLY", 0) == 1;
-  if (!plan_only && (e = msha::launch_digest_parts_planned(a, st)) != hipSuccess)
-    return hip_fail(ctx, "k_digest_parts_planned launch", e);
-  if (!plan_only && d_action_list && (e = msha::launch_parts_fill(a, st)) != hipSuccess)
-    return hip_fail(ctx, "k_parts_fill launch", e);
-  ps.ran = true;
-  ps.last_lists = n_lists;
-  if (!capturing && (e = hipEventRecord(ps.last, st)) != hipSuccess) return hip_fail(ctx, "hipEventRecord", e);
-
-  float ms = 0;
-  uint32_t info[4] = {0, 0, 0, 0};
-  if (timed) {
-    if ((e = hipEventRecord(ev.b, st)) != hipSuccess) return hip_fail(ctx, "hipEventRecord", e);
-    if ((e = hipEventSynchronize(ev.b)) != hipSuccess) return hip_fail(ctx, "hipEventSynchronize", e);
-    if ((e = hipEventElapsedTime(&ms, ev.a, ev.b)) != hipSuccess) return hip_fail(ctx, "hipEventElapsedTime", e);
-    if ((e = hipMemcpy(info, a.info, sizeof info, hipMemcpyDeviceToHost)) != hipSuccess)
-      return hip_fail(ctx, "hipMemcpy", e);
-  }
-  msha_parts_plan_stats& s = ps.stats;
-  s.calls++;
-  s.actions += n_actions;
-  s.lists += n_lists;
-  s.launches_plan += plan_launches;
-  if (!plan_only) s.launches_hash++;
-  if (!plan_only && d_action_list) s.launches_fill++;
-  s.last_lanes = info[0];
-  s.last_blocks = (uint64_t)info[3] << 32 | info[2];
-  s.last_kernel_ms = ms;
-  return MSHA_OK;
+    const float ms = timer.stop();
+    uint32_t info[4] = {0, 0, 0, 0};
+    if (timer.enabled()) HIPCHK(hipMemcpy(info, a.info, sizeof info, hipMemcpyDeviceToHost));
+    msha_parts_plan_stats& s = ps.stats;
+    s.calls++;
+    s.actions += n_actions;
+    s.lists += n_lists;
+    s.launches_plan += plan_launches;
+    if (!plan_only) s.launches_hash++;
+    if (!plan_only && d_action_list) s.launches_fill++;
+    s.last_lanes = info[0];
+    s.last_blocks = (uint64_t)info[3] << 32 | info[2];
+    s.last_kernel_ms = ms;
+  });
 }
 
 int msha_get_parts_plan_stats(const msha_ctx* ctx, msha_parts_plan_stats* out) {
@@ -189,21 +149,18 @@ int msha_parts_plan_read_order(msha_ctx* ctx, uint32_t* order, uint64_t cap, uin
   msha::PartsPlanState& ps = msha::ctx_parts_plan(ctx);
   *lanes = 0;
   if (!ps.ran) return MSHA_OK;
-  msha::CtxDevice d;
-  const int rc = msha::ctx_first_device(ctx, &d);
-  if (rc != MSHA_OK) return rc;
-  hipError_t e;
-  if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(ctx, "hipDeviceSynchronize", e);
-  const uint8_t* ws = static_cast<const uint8_t*>(ps.ws);
-  uint32_t n = 0;
-  if ((e = hipMemcpy(&n, ws, 4, hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail(ctx, "hipMemcpy", e);
-  if (n > ps.last_lists) n = (uint32_t)ps.last_lists;  // the order holds last_lists positions
-  *lanes = n;
-  const uint64_t k = n < cap ? n : cap;
-  const Layout lay(ps.last_lists, false);
-  if (k && (e = hipMemcpy(order, ws + lay.order, 4 * k, hipMemcpyDeviceToHost)) != hipSuccess)
-    return hip_fail(ctx, "hipMemcpy", e);
-  return MSHA_OK;
+  return msha::guard(ctx, [&] {
+    (void)msha::ctx_first_device(ctx);
+    HIPCHK(hipDeviceSynchronize());
+    const uint8_t* ws = static_cast<const uint8_t*>(ps.ws);
+    uint32_t n = 0;
+    HIPCHK(hipMemcpy(&n, ws, 4, hipMemcpyDeviceToHost));
+    if (n > ps.last_lists) n = (uint32_t)ps.last_lists;  // the order holds last_lists positions
+    *lanes = n;
+    const uint64_t k = n < cap ? n : cap;
+    const Layout lay(ps.last_lists, false);
+    if (k) HIPCHK(hipMemcpy(order, ws + lay.order, 4 * k, hipMemcpyDeviceToHost));
+  });
 }
 
 }  // extern "C"

@@ -8,18 +8,15 @@
 // buffer of their own.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstring>
 #include <mutex>
 #include <new>
-#include <numeric>
 #include <string>
 #include <vector>
 
 #include "../../include/mirsha.h"
-#include "ctx_access.hpp"
-#include "kernels.hpp"
+#include "host_call.hpp"
 #include "stream_device.hpp"
+#include "stream_state.hpp"
 
 struct msha_dstreams {
   msha_ctx* ctx = nullptr;
@@ -30,29 +27,12 @@ struct msha_dstreams {
 
 namespace {
 
-constexpr uint8_t kMagic[4] = {'s', 'h', 'a', 0x03};
-constexpr uint64_t kRowBytes = 4 * msha::dstream::kRowDwords;
+namespace ss = msha::sstate;
+
+static_assert(ss::kBytes == MSHA_STREAM_STATE_BYTES, "the exported state is MSHA_STREAM_STATE_BYTES long");
+constexpr uint64_t kRowDwords = msha::dstream::kRowDwords;  // a packed row: state, buffer, length (lo, hi)
+constexpr uint64_t kRowBytes = 4 * kRowDwords;
 constexpr uint64_t kMaxRows = 0xFFFFFFFFull;  // n and n_rows stay below it
-
-int hip_fail(msha_ctx* ctx, const char* what, hipError_t e) {
-  return msha::ctx_fail(ctx, e == hipErrorOutOfMemory ? MSHA_ERR_OUT_OF_MEMORY : MSHA_ERR_HIP,
-                        (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-
-inline uint32_t be32(const uint8_t* p) {
-  return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3];
-}
-inline void put_be32(uint8_t* p, uint32_t v) {
-  p[0] = (uint8_t)(v >> 24), p[1] = (uint8_t)(v >> 16), p[2] = (uint8_t)(v >> 8), p[3] = (uint8_t)v;
-}
-
-struct EventPair {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~EventPair() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
 
 struct DeviceBuf {
   void* p = nullptr;
@@ -68,45 +48,6 @@ void release(msha_dstreams* s) {
   if (s->rows.length) (void)hipFree(s->rows.length);
 }
 
-enum Op { kWrite, kSum, kSnap, kReset };
-
-// One launch on the caller's stream and nothing else. Under MSHA_PARTS_TIMING=1
-// (diagnostic, parts.cpp's convention) the launch is timed with HIP events, which makes
-// the call wait for the kernel; never on a capturing stream.
-template <class Launch>
-int device_call(msha_dstreams* s, Op op, uint64_t n_rows, void* stream, const char* what, Launch&& launch) {
-  msha_ctx* ctx = s->ctx;
-  hipError_t e;
-  if ((e = hipSetDevice(s->dev.id)) != hipSuccess) return hip_fail(ctx, "hipSetDevice", e);
-  const hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->dev.stream;
-  static const bool timing = msha::env_int("MSHA_PARTS_TIMING", 0) == 1;
-  bool timed = false;
-  if (timing) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if ((e = hipStreamIsCapturing(st, &cap)) != hipSuccess) return hip_fail(ctx, "hipStreamIsCapturing", e);
-    timed = cap == hipStreamCaptureStatusNone;
-  }
-  EventPair ev;
-  if (timed) {
-    if ((e = hipEventCreate(&ev.a)) != hipSuccess) return hip_fail(ctx, "hipEventCreate", e);
-    if ((e = hipEventCreate(&ev.b)) != hipSuccess) return hip_fail(ctx, "hipEventCreate", e);
-    if ((e = hipEventRecord(ev.a, st)) != hipSuccess) return hip_fail(ctx, "hipEventRecord", e);
-  }
-  if ((e = launch(st)) != hipSuccess) return hip_fail(ctx, what, e);
-  float ms = 0;
-  if (timed) {
-    if ((e = hipEventRecord(ev.b, st)) != hipSuccess) return hip_fail(ctx, "hipEventRecord", e);
-    if ((e = hipEventSynchronize(ev.b)) != hipSuccess) return hip_fail(ctx, "hipEventSynchronize", e);
-    if ((e = hipEventElapsedTime(&ms, ev.a, ev.b)) != hipSuccess) return hip_fail(ctx, "hipEventElapsedTime", e);
-  }
-  msha_dstreams_stats& t = s->st;
-  (op == kWrite ? t.writes : op == kSum ? t.sums : op == kSnap ? t.snaps : t.resets)++;
-  t.launches++;
-  t.last_rows = n_rows;
-  t.last_kernel_ms = ms;
-  return MSHA_OK;
-}
-
 // The row arguments every device call shares. Call with the lock held.
 int check_rows(msha_dstreams* s, const char* entry, const uint32_t* d_row, uint64_t n_rows) {
   if (n_rows >= kMaxRows)
@@ -117,38 +58,52 @@ int check_rows(msha_dstreams* s, const char* entry, const uint32_t* d_row, uint6
   return MSHA_OK;
 }
 
-bool ids_valid(const msha_dstreams* s, const uint64_t* id, uint64_t k) {
-  if (!id) return k == s->rows.n;
-  for (uint64_t j = 0; j < k; ++j)
-    if (id[j] >= s->rows.n) return false;
-  return true;
+enum Op { kWrite, kSum, kSnap, kReset };
+
+// The rows checked, then one launch on the caller's stream and nothing else (but what
+// MSHA_PARTS_TIMING=1 adds: host_call.hpp LaunchTimer). Call with the lock held.
+template <class Launch>
+int device_call(msha_dstreams* s, const char* entry, Op op, const uint32_t* d_row, uint64_t n_rows, void* stream,
+                const char* what, Launch&& launch) {
+  const int rc = check_rows(s, entry, d_row, n_rows);
+  if (rc != MSHA_OK) return rc;
+  return msha::guard(s->ctx, [&] {
+    msha::CtxDevice d;  // the set's own (s->dev): the context's first device
+    const hipStream_t st = msha::device_entry(s->ctx, entry, stream, &d);
+    msha::LaunchTimer timer(st);
+    msha::launch_check(launch(st), what);
+    const float ms = timer.stop();
+    msha_dstreams_stats& t = s->st;
+    (op == kWrite ? t.writes : op == kSum ? t.sums : op == kSnap ? t.snaps : t.resets)++;
+    t.launches++;
+    t.last_rows = n_rows;
+    t.last_kernel_ms = ms;
+  });
 }
 
 // The streams id[j] (id null: all) as packed rows in host memory, after the device has
-// finished everything enqueued so far.
-int fetch_rows(msha_dstreams* s, const uint64_t* id, uint64_t k, std::vector<uint32_t>* host) {
-  msha_ctx* ctx = s->ctx;
-  hipError_t e;
-  if ((e = hipSetDevice(s->dev.id)) != hipSuccess) return hip_fail(ctx, "hipSetDevice", e);
-  if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(ctx, "hipDeviceSynchronize", e);
-  host->assign(msha::dstream::kRowDwords * k, 0);
-  if (k == 0) return MSHA_OK;
+// finished everything enqueued so far. Inside guard().
+std::vector<uint32_t> fetch_rows(msha_dstreams* s, const uint64_t* id, uint64_t k) {
+  HIPCHK(hipSetDevice(s->dev.id));
+  HIPCHK(hipDeviceSynchronize());
+  std::vector<uint32_t> host(kRowDwords * k, 0);
+  if (k == 0) return host;
   std::vector<uint32_t> id32;
   if (id) id32.assign(id, id + k);  // checked below n < 2^32
   DeviceBuf ids, packed;
-  if (id && (e = hipMalloc(&ids.p, 4 * k)) != hipSuccess) return hip_fail(ctx, "hipMalloc", e);
-  if ((e = hipMalloc(&packed.p, kRowBytes * k)) != hipSuccess) return hip_fail(ctx, "hipMalloc", e);
+  if (id) HIPCHK(hipMalloc(&ids.p, 4 * k));
+  HIPCHK(hipMalloc(&packed.p, kRowBytes * k));
   const hipStream_t q = s->dev.stream;
-  if (id && (e = hipMemcpyAsync(ids.p, id32.data(), 4 * k, hipMemcpyHostToDevice, q)) != hipSuccess)
-    return hip_fail(ctx, "hipMemcpyAsync", e);
-  if ((e = msha::launch_dstream_rows_get(s->rows, static_cast<const uint32_t*>(ids.p), k,
-                                         static_cast<uint32_t*>(packed.p), q)) != hipSuccess)
-    return hip_fail(ctx, "k_dstream_rows_get launch", e);
-  if ((e = hipMemcpyAsync(host->data(), packed.p, kRowBytes * k, hipMemcpyDeviceToHost, q)) != hipSuccess)
-    return hip_fail(ctx, "hipMemcpyAsync", e);
-  if ((e = hipStreamSynchronize(q)) != hipSuccess) return hip_fail(ctx, "hipStreamSynchronize", e);
-  return MSHA_OK;
+  if (id) HIPCHK(hipMemcpyAsync(ids.p, id32.data(), 4 * k, hipMemcpyHostToDevice, q));
+  msha::launch_check(msha::launch_dstream_rows_get(s->rows, static_cast<const uint32_t*>(ids.p), k,
+                                                   static_cast<uint32_t*>(packed.p), q),
+                     "k_dstream_rows_get launch");
+  HIPCHK(hipMemcpyAsync(host.data(), packed.p, kRowBytes * k, hipMemcpyDeviceToHost, q));
+  HIPCHK(hipStreamSynchronize(q));
+  return host;
 }
+
+inline uint64_t row_length(const uint32_t* row) { return (uint64_t)row[25] << 32 | row[24]; }
 
 }  // namespace
 
@@ -164,18 +119,15 @@ int msha_dstreams_create(msha_ctx* ctx, uint64_t n, msha_dstreams** out) {
   if (!s) return msha::ctx_fail(ctx, MSHA_ERR_OUT_OF_MEMORY, "host allocation failed");
   s->ctx = ctx;
   s->rows.n = n;
-  int rc = msha::ctx_first_device(ctx, &s->dev);
-  if (rc == MSHA_OK) {
-    hipError_t e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&s->rows.state), 32 * n)) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&s->rows.tail), 64 * n)) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&s->rows.length), 8 * n)) != hipSuccess)
-      rc = hip_fail(ctx, "hipMalloc", e);
-    else if ((e = msha::launch_dstream_reset(s->rows, nullptr, n, s->dev.err, s->dev.stream)) != hipSuccess)
-      rc = hip_fail(ctx, "k_dstream_reset launch", e);
-    else if ((e = hipStreamSynchronize(s->dev.stream)) != hipSuccess)
-      rc = hip_fail(ctx, "hipStreamSynchronize", e);
-  }
+  const int rc = msha::guard(ctx, [&] {
+    s->dev = msha::ctx_first_device(ctx);
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->rows.state), 32 * n));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->rows.tail), 64 * n));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->rows.length), 8 * n));
+    msha::launch_check(msha::launch_dstream_reset(s->rows, nullptr, n, s->dev.err, s->dev.stream),
+                       "k_dstream_reset launch");
+    HIPCHK(hipStreamSynchronize(s->dev.stream));
+  });
   if (rc != MSHA_OK) {
     release(s);
     delete s;
@@ -197,6 +149,7 @@ void msha_dstreams_destroy(msha_dstreams* s) {
 int msha_dstreams_write_device(msha_dstreams* s, const uint8_t* d_arena, const uint64_t* d_part_off,
                                const uint64_t* d_part_len, const uint64_t* d_row_part_begin, const uint32_t* d_row,
                                uint64_t n_rows, void* stream) {
+  static const char* const kEntry = "msha_dstreams_write_device";
   if (!s) return MSHA_ERR_INVALID_ARG;
   if (n_rows == 0) return MSHA_OK;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
@@ -204,10 +157,8 @@ int msha_dstreams_write_device(msha_dstreams* s, const uint8_t* d_arena, const u
     return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
   // the kernel reads aligned 16-byte granules of offsets: they must be granules of addresses
   if (reinterpret_cast<uintptr_t>(d_arena) % MSHA_DEVICE_ALIGN)
-    return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "msha_dstreams_write_device: d_arena must be 16-byte aligned");
-  const int rc = check_rows(s, "msha_dstreams_write_device", d_row, n_rows);
-  if (rc != MSHA_OK) return rc;
-  return device_call(s, kWrite, n_rows, stream, "k_dstream_write launch", [&](hipStream_t st) {
+    return msha::bad_arg(s->ctx, kEntry, "d_arena must be 16-byte aligned");
+  return device_call(s, kEntry, kWrite, d_row, n_rows, stream, "k_dstream_write launch", [&](hipStream_t st) {
     return msha::launch_dstream_write(s->rows, d_arena, d_part_off, d_part_len, d_row_part_begin, d_row, n_rows,
                                       s->dev.err, st);
   });
@@ -218,9 +169,8 @@ int msha_dstreams_sum_device(msha_dstreams* s, const uint32_t* d_row, uint64_t n
   if (n_rows == 0) return MSHA_OK;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
   if (!d_out) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
-  const int rc = check_rows(s, "msha_dstreams_sum_device", d_row, n_rows);
-  if (rc != MSHA_OK) return rc;
-  return device_call(s, kSum, n_rows, stream, "k_dstream_finish launch", [&](hipStream_t st) {
+  return device_call(s, "msha_dstreams_sum_device", kSum, d_row, n_rows, stream, "k_dstream_finish launch",
+                     [&](hipStream_t st) {
     return msha::launch_dstream_finish(s->rows, d_row, n_rows, d_out, false, s->dev.err, st);
   });
 }
@@ -230,9 +180,8 @@ int msha_dstreams_snap_device(msha_dstreams* s, const uint32_t* d_row, uint64_t 
   if (n_rows == 0) return MSHA_OK;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
   if (!d_out) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
-  const int rc = check_rows(s, "msha_dstreams_snap_device", d_row, n_rows);
-  if (rc != MSHA_OK) return rc;
-  return device_call(s, kSnap, n_rows, stream, "k_dstream_finish launch", [&](hipStream_t st) {
+  return device_call(s, "msha_dstreams_snap_device", kSnap, d_row, n_rows, stream, "k_dstream_finish launch",
+                     [&](hipStream_t st) {
     return msha::launch_dstream_finish(s->rows, d_row, n_rows, d_out, true, s->dev.err, st);
   });
 }
@@ -241,9 +190,8 @@ int msha_dstreams_reset_device(msha_dstreams* s, const uint32_t* d_row, uint64_t
   if (!s) return MSHA_ERR_INVALID_ARG;
   if (n_rows == 0) return MSHA_OK;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
-  const int rc = check_rows(s, "msha_dstreams_reset_device", d_row, n_rows);
-  if (rc != MSHA_OK) return rc;
-  return device_call(s, kReset, n_rows, stream, "k_dstream_reset launch", [&](hipStream_t st) {
+  return device_call(s, "msha_dstreams_reset_device", kReset, d_row, n_rows, stream, "k_dstream_reset launch",
+                     [&](hipStream_t st) {
     return msha::launch_dstream_reset(s->rows, d_row, n_rows, s->dev.err, st);
   });
 }
@@ -251,106 +199,68 @@ int msha_dstreams_reset_device(msha_dstreams* s, const uint32_t* d_row, uint64_t
 int msha_dstreams_length(msha_dstreams* s, const uint64_t* id, uint64_t k, uint64_t* out) {
   if (!s) return MSHA_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
-  if (!ids_valid(s, id, k))
-    return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "msha_dstreams_length: stream id out of range (id NULL: k must be n)");
+  if (!ss::ids_valid(s->rows.n, id, k))
+    return msha::bad_arg(s->ctx, "msha_dstreams_length", "stream id out of range (id NULL: k must be n)");
   if (k && !out) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
-  try {
-    std::vector<uint32_t> rows;
-    const int rc = fetch_rows(s, id, k, &rows);
-    if (rc != MSHA_OK) return rc;
-    for (uint64_t j = 0; j < k; ++j) {
-      const uint32_t* p = &rows[msha::dstream::kRowDwords * j];
-      out[j] = (uint64_t)p[25] << 32 | p[24];
-    }
-  } catch (const std::bad_alloc&) {
-    return msha::ctx_fail(s->ctx, MSHA_ERR_OUT_OF_MEMORY, "host allocation failed");
-  }
-  return MSHA_OK;
+  return msha::guard(s->ctx, [&] {
+    const std::vector<uint32_t> rows = fetch_rows(s, id, k);
+    for (uint64_t j = 0; j < k; ++j) out[j] = row_length(&rows[kRowDwords * j]);
+  });
 }
 
 int msha_dstreams_export(msha_dstreams* s, const uint64_t* id, uint64_t k, uint8_t* out) {
   if (!s) return MSHA_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
-  if (!ids_valid(s, id, k))
-    return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "msha_dstreams_export: stream id out of range (id NULL: k must be n)");
+  if (!ss::ids_valid(s->rows.n, id, k))
+    return msha::bad_arg(s->ctx, "msha_dstreams_export", "stream id out of range (id NULL: k must be n)");
   if (k && !out) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
-  try {
-    std::vector<uint32_t> rows;
-    const int rc = fetch_rows(s, id, k, &rows);
-    if (rc != MSHA_OK) return rc;
+  return msha::guard(s->ctx, [&] {
+    const std::vector<uint32_t> rows = fetch_rows(s, id, k);
     for (uint64_t j = 0; j < k; ++j) {
-      const uint32_t* p = &rows[msha::dstream::kRowDwords * j];
-      uint8_t* o = out + MSHA_STREAM_STATE_BYTES * j;
-      const uint64_t len = (uint64_t)p[25] << 32 | p[24];
-      std::memcpy(o, kMagic, 4);
-      for (int w = 0; w < 8; ++w) put_be32(o + 4 + 4 * w, p[w]);
-      std::memset(o + 36, 0, 64);
-      std::memcpy(o + 36, p + 8, len % 64);  // little-endian host, as the GPU
-      put_be32(o + 100, (uint32_t)(len >> 32));
-      put_be32(o + 104, (uint32_t)len);
+      const uint32_t* p = &rows[kRowDwords * j];
+      // the buffer's bytes as they lie in the row: little-endian host, as the GPU
+      ss::encode(p, reinterpret_cast<const uint8_t*>(p + 8), row_length(p), out + ss::kBytes * j);
     }
-  } catch (const std::bad_alloc&) {
-    return msha::ctx_fail(s->ctx, MSHA_ERR_OUT_OF_MEMORY, "host allocation failed");
-  }
-  return MSHA_OK;
+  });
 }
 
 int msha_dstreams_import(msha_dstreams* s, const uint64_t* id, uint64_t k, const uint8_t* in) {
   if (!s) return MSHA_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
-  msha_ctx* ctx = s->ctx;
-  if (!ids_valid(s, id, k))
-    return msha::ctx_fail(ctx, MSHA_ERR_INVALID_ARG, "msha_dstreams_import: stream id out of range (id NULL: k must be n)");
-  if (k && !in) return msha::ctx_fail(ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
+  if (!ss::ids_valid(s->rows.n, id, k))
+    return msha::bad_arg(s->ctx, "msha_dstreams_import", "stream id out of range (id NULL: k must be n)");
+  if (k && !in) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
   for (uint64_t j = 0; j < k; ++j)
-    if (std::memcmp(in + MSHA_STREAM_STATE_BYTES * j, kMagic, 4) != 0)
-      return msha::ctx_fail(ctx, MSHA_ERR_INVALID_ARG, "msha_dstreams_import: not an exported SHA-256 state (magic)");
-  try {
-    // Sequential UnmarshalBinary: of the entries that name one stream the last wins (as
-    // msha_streams_import). Only that entry goes to the device: two rows for one stream
-    // in one launch would be stored by two lanes in no order.
-    std::vector<uint64_t> last(k);
-    std::iota(last.begin(), last.end(), uint64_t(0));
-    if (id) {
-      std::vector<uint64_t> ord(last);
-      std::stable_sort(ord.begin(), ord.end(), [&](uint64_t a, uint64_t b) { return id[a] < id[b]; });
-      last.clear();
-      for (uint64_t a = 0; a < k; ++a)
-        if (a + 1 == k || id[ord[a + 1]] != id[ord[a]]) last.push_back(ord[a]);
-      std::sort(last.begin(), last.end());
-    }
+    if (!ss::has_magic(in + ss::kBytes * j))
+      return msha::bad_arg(s->ctx, "msha_dstreams_import", "not an exported SHA-256 state (magic)");
+  return msha::guard(s->ctx, [&] {
+    // Only the entry that takes effect goes to the device: two rows for one stream in one
+    // launch would be stored by two lanes in no order.
+    const std::vector<uint64_t> last = ss::last_wins(id, k);
     const uint64_t m = last.size();
-    std::vector<uint32_t> id32(m), rows(msha::dstream::kRowDwords * m, 0);
+    std::vector<uint32_t> id32(m), rows(kRowDwords * m, 0);
     for (uint64_t j = 0; j < m; ++j) {
-      const uint8_t* p = in + MSHA_STREAM_STATE_BYTES * last[j];
-      uint32_t* r = &rows[msha::dstream::kRowDwords * j];
+      uint32_t* r = &rows[kRowDwords * j];
+      uint64_t len = 0;
       id32[j] = (uint32_t)(id ? id[last[j]] : last[j]);
-      for (int w = 0; w < 8; ++w) r[w] = be32(p + 4 + 4 * w);
-      const uint64_t len = (uint64_t)be32(p + 100) << 32 | be32(p + 104);
-      std::memcpy(r + 8, p + 36, len % 64);  // bytes past length % 64 are stored as zeros
+      ss::decode(in + ss::kBytes * last[j], r, reinterpret_cast<uint8_t*>(r + 8), &len);
       r[24] = (uint32_t)len;
       r[25] = (uint32_t)(len >> 32);
     }
-    hipError_t e;
-    if ((e = hipSetDevice(s->dev.id)) != hipSuccess) return hip_fail(ctx, "hipSetDevice", e);
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(ctx, "hipDeviceSynchronize", e);
-    if (m == 0) return MSHA_OK;
+    HIPCHK(hipSetDevice(s->dev.id));
+    HIPCHK(hipDeviceSynchronize());
+    if (m == 0) return;
     DeviceBuf ids, packed;
-    if ((e = hipMalloc(&ids.p, 4 * m)) != hipSuccess) return hip_fail(ctx, "hipMalloc", e);
-    if ((e = hipMalloc(&packed.p, kRowBytes * m)) != hipSuccess) return hip_fail(ctx, "hipMalloc", e);
+    HIPCHK(hipMalloc(&ids.p, 4 * m));
+    HIPCHK(hipMalloc(&packed.p, kRowBytes * m));
     const hipStream_t q = s->dev.stream;
-    if ((e = hipMemcpyAsync(ids.p, id32.data(), 4 * m, hipMemcpyHostToDevice, q)) != hipSuccess)
-      return hip_fail(ctx, "hipMemcpyAsync", e);
-    if ((e = hipMemcpyAsync(packed.p, rows.data(), kRowBytes * m, hipMemcpyHostToDevice, q)) != hipSuccess)
-      return hip_fail(ctx, "hipMemcpyAsync", e);
-    if ((e = msha::launch_dstream_rows_set(s->rows, static_cast<const uint32_t*>(ids.p), m,
-                                           static_cast<const uint32_t*>(packed.p), q)) != hipSuccess)
-      return hip_fail(ctx, "k_dstream_rows_set launch", e);
-    if ((e = hipStreamSynchronize(q)) != hipSuccess) return hip_fail(ctx, "hipStreamSynchronize", e);
-  } catch (const std::bad_alloc&) {
-    return msha::ctx_fail(ctx, MSHA_ERR_OUT_OF_MEMORY, "host allocation failed");
-  }
-  return MSHA_OK;
+    HIPCHK(hipMemcpyAsync(ids.p, id32.data(), 4 * m, hipMemcpyHostToDevice, q));
+    HIPCHK(hipMemcpyAsync(packed.p, rows.data(), kRowBytes * m, hipMemcpyHostToDevice, q));
+    msha::launch_check(msha::launch_dstream_rows_set(s->rows, static_cast<const uint32_t*>(ids.p), m,
+                                                     static_cast<const uint32_t*>(packed.p), q),
+                       "k_dstream_rows_set launch");
+    HIPCHK(hipStreamSynchronize(q));
+  });
 }
 
 int msha_dstreams_get_stats(const msha_dstreams* s, msha_dstreams_stats* out) {

@@ -5,37 +5,22 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
-#include <exception>
 #include <mutex>
 #include <new>
-#include <numeric>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
 #include "../../include/mirsha.h"
-#include "ctx_access.hpp"
-#include "kernels.hpp"
+#include "host_call.hpp"
 #include "stream_pack.hpp"
+#include "stream_state.hpp"
 
 namespace {
 
 namespace sp = msha::spack;
+namespace ss = msha::sstate;
 
-struct HipFailure : std::runtime_error {
-  int code;
-  HipFailure(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-#define SCHK(expr)                                                                        \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      throw HipFailure(e_ == hipErrorOutOfMemory ? MSHA_ERR_OUT_OF_MEMORY : MSHA_ERR_HIP, \
-                       std::string(#expr) + ": " + hipGetErrorString(e_));                \
-  } while (0)
+static_assert(ss::kBytes == MSHA_STREAM_STATE_BYTES, "the exported state is MSHA_STREAM_STATE_BYTES long");
 
 // A device buffer and its pinned host twin, grown on demand up to what a piece needs.
 struct Staged {
@@ -46,8 +31,8 @@ struct Staged {
     if (bytes <= cap) return;
     release();
     const uint64_t want = std::max<uint64_t>(bytes, 4096);
-    SCHK(hipMalloc(&d, want));
-    SCHK(hipHostMalloc(&h, want, hipHostMallocPortable));
+    HIPCHK(hipMalloc(&d, want));
+    HIPCHK(hipHostMalloc(&h, want, hipHostMallocPortable));
     cap = want;
   }
   void release() {
@@ -60,15 +45,7 @@ struct Staged {
   template <class T> T* host(uint64_t byte_off = 0) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(h) + byte_off); }
 };
 
-constexpr uint8_t kMagic[4] = {'s', 'h', 'a', 0x03};
-
 inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-inline uint32_t be32(const uint8_t* p) {
-  return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3];
-}
-inline void put_be32(uint8_t* p, uint32_t v) {
-  p[0] = (uint8_t)(v >> 24), p[1] = (uint8_t)(v >> 16), p[2] = (uint8_t)(v >> 8), p[3] = (uint8_t)v;
-}
 
 }  // namespace
 
@@ -102,41 +79,34 @@ struct MetaLayout {
   }
 };
 
+// A call on the set: msha::guard() (host_call.hpp) on the set's device. A failure
+// leaves the set failed (marks_failed), except a host allocation that failed.
 template <class F>
 int run(msha_streams* s, bool marks_failed, F&& f) {
-  msha_ctx* ctx = s->ctx;
-  try {
-    SCHK(hipSetDevice(s->dev.id));
-    f();
-    msha::ctx_fail(ctx, MSHA_OK, nullptr);
-    return MSHA_OK;
-  } catch (const HipFailure& e) {
-    if (marks_failed) s->failed = true;
-    return msha::ctx_fail(ctx, e.code, e.what());
-  } catch (const std::bad_alloc&) {
-    return msha::ctx_fail(ctx, MSHA_ERR_OUT_OF_MEMORY, "host allocation failed");
-  } catch (const std::exception& e) {
-    if (marks_failed) s->failed = true;
-    return msha::ctx_fail(ctx, MSHA_ERR_HIP, e.what());
-  }
+  bool host_oom = false;
+  const int rc = msha::guard(s->ctx, [&] {
+    try {
+      HIPCHK(hipSetDevice(s->dev.id));
+      f();
+    } catch (const std::bad_alloc&) {
+      host_oom = true;
+      throw;
+    }
+  });
+  if (rc != MSHA_OK && marks_failed && !host_oom) s->failed = true;
+  return rc;
 }
 
 int failed_set(msha_streams* s) {
   return msha::ctx_fail(s->ctx, MSHA_ERR_HIP, "stream set failed earlier: msha_streams_reset(set, NULL, 0) first");
 }
 
-bool ids_valid(const msha_streams* s, const uint64_t* id, uint64_t k) {
-  if (!id) return k == s->n;
-  for (uint64_t j = 0; j < k; ++j)
-    if (id[j] >= s->n) return false;
-  return true;
-}
 inline uint64_t id_at(const uint64_t* id, uint64_t j) { return id ? id[j] : j; }
 
 // The kernel time of the launch between ev0 and ev1 (both recorded, stream synchronised).
 void note_launch(msha_streams* s, int mode, uint64_t lanes) {
   float ms = 0;
-  SCHK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+  HIPCHK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
   s->st.last_kernel_ms = ms;
   s->st.last_load_mode = (uint32_t)mode;
   s->st.last_lanes = (uint32_t)std::min<uint64_t>(lanes, 0xFFFFFFFFu);
@@ -151,16 +121,16 @@ void set_rows(msha_streams* s, const uint64_t* id, uint64_t k, const uint32_t* v
     s->meta.ensure(ml.bytes);
     uint32_t* row = s->meta.host<uint32_t>(ml.row);
     for (uint64_t j = 0; j < m; ++j) row[j] = (uint32_t)id_at(id, a + j);
-    SCHK(hipMemcpyAsync(s->meta.dev<uint8_t>(ml.row), row, 4 * m, hipMemcpyHostToDevice, q));
+    HIPCHK(hipMemcpyAsync(s->meta.dev<uint8_t>(ml.row), row, 4 * m, hipMemcpyHostToDevice, q));
     const uint32_t* dv = nullptr;
     if (vals) {
       s->out.ensure(32 * m);
       std::memcpy(s->out.h, vals + 8 * a, 32 * m);
-      SCHK(hipMemcpyAsync(s->out.d, s->out.h, 32 * m, hipMemcpyHostToDevice, q));
+      HIPCHK(hipMemcpyAsync(s->out.d, s->out.h, 32 * m, hipMemcpyHostToDevice, q));
       dv = s->out.dev<uint32_t>();
     }
-    SCHK(msha::launch_stream_rows_set(s->d_state, s->meta.dev<uint32_t>(ml.row), dv, m, q));
-    SCHK(hipStreamSynchronize(q));
+    HIPCHK(msha::launch_stream_rows_set(s->d_state, s->meta.dev<uint32_t>(ml.row), dv, m, q));
+    HIPCHK(hipStreamSynchronize(q));
   }
 }
 
@@ -189,16 +159,15 @@ int msha_streams_create(msha_ctx* ctx, uint64_t n, uint64_t staging_bytes, msha_
   s->n = n;
   s->staging = sp::staging_bound(staging_bytes);
   s->piece_lanes = s->staging / sp::kBlock;
-  int rc = msha::ctx_first_device(ctx, &s->dev);
-  if (rc == MSHA_OK)
-    rc = run(s, false, [&] {
-      s->length.assign(n, 0);
-      s->tail.assign(64 * n, 0);
-      SCHK(hipMalloc(reinterpret_cast<void**>(&s->d_state), 32 * n));
-      SCHK(hipEventCreate(&s->ev0));
-      SCHK(hipEventCreate(&s->ev1));
-      set_rows(s, nullptr, n, nullptr);
-    });
+  const int rc = msha::guard(ctx, [&] {
+    s->dev = msha::ctx_first_device(ctx);
+    s->length.assign(n, 0);
+    s->tail.assign(64 * n, 0);
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->d_state), 32 * n));
+    HIPCHK(hipEventCreate(&s->ev0));
+    HIPCHK(hipEventCreate(&s->ev1));
+    set_rows(s, nullptr, n, nullptr);
+  });
   if (rc != MSHA_OK) {
     release(s);
     delete s;
@@ -254,15 +223,15 @@ int msha_streams_write(msha_streams* s, const uint8_t* arena, uint64_t arena_len
         hw[j] = p.lanes[j].nblocks;
         hr[j] = (uint32_t)p.lanes[j].id;
       }
-      SCHK(hipMemcpyAsync(s->stage.d, hs, p.bytes, hipMemcpyHostToDevice, q));
-      SCHK(hipMemcpyAsync(s->meta.d, s->meta.h, ml.bytes, hipMemcpyHostToDevice, q));
+      HIPCHK(hipMemcpyAsync(s->stage.d, hs, p.bytes, hipMemcpyHostToDevice, q));
+      HIPCHK(hipMemcpyAsync(s->meta.d, s->meta.h, ml.bytes, hipMemcpyHostToDevice, q));
       int mode = 0;
-      SCHK(hipEventRecord(s->ev0, q));
-      SCHK(msha::launch_stream_absorb(s->d_state, s->stage.dev<uint8_t>(), s->meta.dev<uint64_t>(ml.off),
+      HIPCHK(hipEventRecord(s->ev0, q));
+      HIPCHK(msha::launch_stream_absorb(s->d_state, s->stage.dev<uint8_t>(), s->meta.dev<uint64_t>(ml.off),
                                       s->meta.dev<uint64_t>(ml.work), s->meta.dev<uint32_t>(ml.row), lanes,
                                       s->dev.err, s->dev.cus, q, &mode));
-      SCHK(hipEventRecord(s->ev1, q));
-      SCHK(hipStreamSynchronize(q));
+      HIPCHK(hipEventRecord(s->ev1, q));
+      HIPCHK(hipStreamSynchronize(q));
       note_launch(s, mode, lanes);
       s->st.launches_absorb++;
       s->st.pieces++;
@@ -281,7 +250,7 @@ int msha_streams_sum(msha_streams* s, const uint64_t* id, uint64_t k, uint8_t* o
   if (!s) return MSHA_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
   if (s->failed) return failed_set(s);
-  if (!ids_valid(s, id, k)) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "stream id out of range (id NULL: k must be n)");
+  if (!ss::ids_valid(s->n, id, k)) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "stream id out of range (id NULL: k must be n)");
   if (k && !out) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
   return run(s, true, [&] {
     hipStream_t q = s->dev.stream;
@@ -307,17 +276,17 @@ int msha_streams_sum(msha_streams* s, const uint64_t* id, uint64_t k, uint8_t* o
         hr[j] = (uint32_t)r;
         blocks += t < 56 ? 1 : 2;
       }
-      SCHK(hipMemcpyAsync(s->stage.d, hs, 64 * m, hipMemcpyHostToDevice, q));
-      SCHK(hipMemcpyAsync(s->meta.d, s->meta.h, ml.bytes, hipMemcpyHostToDevice, q));
+      HIPCHK(hipMemcpyAsync(s->stage.d, hs, 64 * m, hipMemcpyHostToDevice, q));
+      HIPCHK(hipMemcpyAsync(s->meta.d, s->meta.h, ml.bytes, hipMemcpyHostToDevice, q));
       int mode = 0;
-      SCHK(hipEventRecord(s->ev0, q));
-      SCHK(msha::launch_stream_finish(s->d_state, s->meta.dev<uint64_t>(ml.prefix), s->stage.dev<uint8_t>(),
+      HIPCHK(hipEventRecord(s->ev0, q));
+      HIPCHK(msha::launch_stream_finish(s->d_state, s->meta.dev<uint64_t>(ml.prefix), s->stage.dev<uint8_t>(),
                                       s->meta.dev<uint64_t>(ml.off), s->meta.dev<uint64_t>(ml.work),
                                       s->meta.dev<uint32_t>(ml.row), m, s->out.dev<uint8_t>(), s->dev.err,
                                       s->dev.cus, q, &mode));
-      SCHK(hipEventRecord(s->ev1, q));
-      SCHK(hipMemcpyAsync(s->out.h, s->out.d, 32 * m, hipMemcpyDeviceToHost, q));
-      SCHK(hipStreamSynchronize(q));
+      HIPCHK(hipEventRecord(s->ev1, q));
+      HIPCHK(hipMemcpyAsync(s->out.h, s->out.d, 32 * m, hipMemcpyDeviceToHost, q));
+      HIPCHK(hipStreamSynchronize(q));
       note_launch(s, mode, m);
       std::memcpy(out + 32 * a, s->out.h, 32 * m);
       s->st.launches_finish++;
@@ -332,7 +301,7 @@ int msha_streams_reset(msha_streams* s, const uint64_t* id, uint64_t k) {
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
   if (id && s->failed) return failed_set(s);
   if (!id) k = s->n;
-  if (!ids_valid(s, id, k)) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "stream id out of range");
+  if (!ss::ids_valid(s->n, id, k)) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "stream id out of range");
   const int rc = run(s, true, [&] {
     set_rows(s, id, k, nullptr);
     for (uint64_t j = 0; j < k; ++j) {
@@ -348,7 +317,7 @@ int msha_streams_reset(msha_streams* s, const uint64_t* id, uint64_t k) {
 int msha_streams_length(const msha_streams* s, const uint64_t* id, uint64_t k, uint64_t* out) {
   if (!s) return MSHA_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
-  if (!ids_valid(s, id, k) || (k && !out)) return MSHA_ERR_INVALID_ARG;
+  if (!ss::ids_valid(s->n, id, k) || (k && !out)) return MSHA_ERR_INVALID_ARG;
   for (uint64_t j = 0; j < k; ++j) out[j] = s->length[id_at(id, j)];
   return MSHA_OK;
 }
@@ -357,7 +326,7 @@ int msha_streams_export(msha_streams* s, const uint64_t* id, uint64_t k, uint8_t
   if (!s) return MSHA_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
   if (s->failed) return failed_set(s);
-  if (!ids_valid(s, id, k)) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "stream id out of range (id NULL: k must be n)");
+  if (!ss::ids_valid(s->n, id, k)) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "stream id out of range (id NULL: k must be n)");
   if (k && !out) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
   return run(s, true, [&] {
     hipStream_t q = s->dev.stream;
@@ -368,21 +337,14 @@ int msha_streams_export(msha_streams* s, const uint64_t* id, uint64_t k, uint8_t
       s->out.ensure(32 * m);
       uint32_t* hr = s->meta.host<uint32_t>(ml.row);
       for (uint64_t j = 0; j < m; ++j) hr[j] = (uint32_t)id_at(id, a + j);
-      SCHK(hipMemcpyAsync(s->meta.dev<uint8_t>(ml.row), hr, 4 * m, hipMemcpyHostToDevice, q));
-      SCHK(msha::launch_stream_rows_get(s->d_state, s->meta.dev<uint32_t>(ml.row), s->out.dev<uint32_t>(), m, q));
-      SCHK(hipMemcpyAsync(s->out.h, s->out.d, 32 * m, hipMemcpyDeviceToHost, q));
-      SCHK(hipStreamSynchronize(q));
+      HIPCHK(hipMemcpyAsync(s->meta.dev<uint8_t>(ml.row), hr, 4 * m, hipMemcpyHostToDevice, q));
+      HIPCHK(msha::launch_stream_rows_get(s->d_state, s->meta.dev<uint32_t>(ml.row), s->out.dev<uint32_t>(), m, q));
+      HIPCHK(hipMemcpyAsync(s->out.h, s->out.d, 32 * m, hipMemcpyDeviceToHost, q));
+      HIPCHK(hipStreamSynchronize(q));
       const uint32_t* hv = s->out.host<uint32_t>();
       for (uint64_t j = 0; j < m; ++j) {
         const uint64_t r = id_at(id, a + j);
-        uint8_t* o = out + MSHA_STREAM_STATE_BYTES * (a + j);
-        std::memcpy(o, kMagic, 4);
-        for (int w = 0; w < 8; ++w) put_be32(o + 4 + 4 * w, hv[8 * j + w]);
-        const uint64_t t = s->length[r] % 64;
-        std::memset(o + 36, 0, 64);
-        std::memcpy(o + 36, &s->tail[64 * r], t);
-        put_be32(o + 100, (uint32_t)(s->length[r] >> 32));
-        put_be32(o + 104, (uint32_t)s->length[r]);
+        ss::encode(hv + 8 * j, &s->tail[64 * r], s->length[r], out + ss::kBytes * (a + j));
       }
     }
   });
@@ -392,41 +354,28 @@ int msha_streams_import(msha_streams* s, const uint64_t* id, uint64_t k, const u
   if (!s) return MSHA_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
   if (s->failed) return failed_set(s);
-  if (!ids_valid(s, id, k)) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "stream id out of range (id NULL: k must be n)");
+  if (!ss::ids_valid(s->n, id, k)) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "stream id out of range (id NULL: k must be n)");
   if (k && !in) return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
   for (uint64_t j = 0; j < k; ++j)
-    if (std::memcmp(in + MSHA_STREAM_STATE_BYTES * j, kMagic, 4) != 0)
+    if (!ss::has_magic(in + ss::kBytes * j))
       return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "not an exported SHA-256 state (magic)");
   return run(s, true, [&] {
-    // Sequential UnmarshalBinary: of the entries that name one stream the last wins,
-    // for state, buffer and length alike. Only that entry goes to the device: two
-    // rows for one stream in one k_stream_rows_set launch would be stored by two
-    // lanes in no order. `last`: the entries that take effect, in call order.
-    std::vector<uint64_t> last(k);
-    std::iota(last.begin(), last.end(), uint64_t(0));
-    if (id) {
-      std::vector<uint64_t> ord(last);
-      std::stable_sort(ord.begin(), ord.end(), [&](uint64_t a, uint64_t b) { return id[a] < id[b]; });
-      last.clear();
-      for (uint64_t a = 0; a < k; ++a)
-        if (a + 1 == k || id[ord[a + 1]] != id[ord[a]]) last.push_back(ord[a]);
-      std::sort(last.begin(), last.end());
-    }
+    // Of the entries that name one stream the last wins, for state, buffer and length
+    // alike. Only that entry goes to the device: two rows for one stream in one
+    // k_stream_rows_set launch would be stored by two lanes in no order.
+    const std::vector<uint64_t> last = ss::last_wins(id, k);
     const uint64_t m = last.size();
-    std::vector<uint64_t> ids(m);
+    std::vector<uint64_t> ids(m), lens(m);
     std::vector<uint32_t> vals(8 * m);
+    std::vector<uint8_t> bufs(64 * m);
     for (uint64_t j = 0; j < m; ++j) {
       ids[j] = id_at(id, last[j]);
-      for (int w = 0; w < 8; ++w) vals[8 * j + w] = be32(in + MSHA_STREAM_STATE_BYTES * last[j] + 4 + 4 * w);
+      ss::decode(in + ss::kBytes * last[j], &vals[8 * j], &bufs[64 * j], &lens[j]);
     }
     set_rows(s, m ? ids.data() : nullptr, m, vals.data());
     for (uint64_t j = 0; j < m; ++j) {
-      const uint64_t r = ids[j];
-      const uint8_t* p = in + MSHA_STREAM_STATE_BYTES * last[j];
-      const uint64_t L = (uint64_t)be32(p + 100) << 32 | be32(p + 104);
-      s->length[r] = L;
-      std::memset(&s->tail[64 * r], 0, 64);
-      std::memcpy(&s->tail[64 * r], p + 36, L % 64);
+      s->length[ids[j]] = lens[j];
+      std::memcpy(&s->tail[64 * ids[j]], &bufs[64 * j], 64);
     }
   });
 }
@@ -444,13 +393,12 @@ int msha_absorb_device(msha_ctx* ctx, uint32_t* d_state, const uint8_t* d_arena,
   if (n == 0) return MSHA_OK;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(ctx));
   if (!d_state || !d_arena || !d_off || !d_nblocks) return msha::ctx_fail(ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
-  msha::CtxDevice d;
-  const int rc = msha::ctx_first_device(ctx, &d);
-  if (rc != MSHA_OK) return rc;
-  const hipError_t e = msha::launch_stream_absorb(d_state, d_arena, d_off, d_nblocks, nullptr, n, d.err, d.cus,
-                                                  stream ? static_cast<hipStream_t>(stream) : d.stream);
-  if (e != hipSuccess) return msha::ctx_fail(ctx, MSHA_ERR_HIP, hipGetErrorString(e));
-  return MSHA_OK;
+  return msha::guard(ctx, [&] {
+    msha::CtxDevice d;
+    const hipStream_t st = msha::device_entry(ctx, "msha_absorb_device", stream, &d);
+    msha::launch_check(msha::launch_stream_absorb(d_state, d_arena, d_off, d_nblocks, nullptr, n, d.err, d.cus, st),
+                       "k_stream_absorb launch");
+  });
 }
 
 int msha_finish_device(msha_ctx* ctx, const uint32_t* d_state, const uint64_t* d_prefix, const uint8_t* d_arena,
@@ -459,13 +407,13 @@ int msha_finish_device(msha_ctx* ctx, const uint32_t* d_state, const uint64_t* d
   if (n == 0) return MSHA_OK;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(ctx));
   if (!d_arena || !d_off || !d_len || !d_out) return msha::ctx_fail(ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
-  msha::CtxDevice d;
-  const int rc = msha::ctx_first_device(ctx, &d);
-  if (rc != MSHA_OK) return rc;
-  const hipError_t e = msha::launch_stream_finish(d_state, d_prefix, d_arena, d_off, d_len, nullptr, n, d_out, d.err,
-                                                  d.cus, stream ? static_cast<hipStream_t>(stream) : d.stream);
-  if (e != hipSuccess) return msha::ctx_fail(ctx, MSHA_ERR_HIP, hipGetErrorString(e));
-  return MSHA_OK;
+  return msha::guard(ctx, [&] {
+    msha::CtxDevice d;
+    const hipStream_t st = msha::device_entry(ctx, "msha_finish_device", stream, &d);
+    msha::launch_check(
+        msha::launch_stream_finish(d_state, d_prefix, d_arena, d_off, d_len, nullptr, n, d_out, d.err, d.cus, st),
+        "k_stream_finish launch");
+  });
 }
 
 }  // extern "C"

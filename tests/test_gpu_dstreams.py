@@ -404,3 +404,91 @@ def test_graph_capture_replays_append(engine):
         assert s.lengths().tolist() == [3 * len(x) for x in once]
         engine.device_status()
         del g
+
+
+def test_timing_is_read_at_each_call(engine, monkeypatch):
+    """MSHA_PARTS_TIMING is read by every write and sum, not once in the process: off, on
+    and off again inside one process, the digests and the other counters the same each time."""
+    rng = np.random.default_rng(72)
+    n = 70
+    rows_bytes = [[rng.bytes(40)] for _ in range(n)]
+    batch = _packed(rows_bytes, rng)
+    d = [_dev(x) for x in batch]
+
+    def round_(s, times):
+        """One write and one sum, digests and counters checked; the two calls' last_kernel_ms."""
+        before = s.stats()
+        s.write_device(*d)
+        mid = s.stats()
+        got = _sum(s)
+        after = s.stats()
+        engine.device_status()
+        want = np.frombuffer(b"".join(hashlib.sha256(r[0] * times).digest() for r in rows_bytes), np.uint8)
+        assert _bad_rows(got, want.reshape(n, 32)) == [], times
+        assert [after[k] - before[k] for k in ("writes", "sums", "snaps", "resets", "launches")] == [1, 1, 0, 0, 2]
+        assert mid["launches"] - before["launches"] == 1 and mid["last_rows"] == after["last_rows"] == n
+        return mid["last_kernel_ms"], after["last_kernel_ms"]
+
+    with DeviceStreamSet(engine, n) as s:
+        monkeypatch.delenv("MSHA_PARTS_TIMING", raising=False)
+        assert round_(s, 1) == (0.0, 0.0)
+        monkeypatch.setenv("MSHA_PARTS_TIMING", "1")
+        w_ms, s_ms = round_(s, 2)
+        assert w_ms > 0 and s_ms > 0
+        monkeypatch.delenv("MSHA_PARTS_TIMING")
+        assert round_(s, 3) == (0.0, 0.0)
+        assert s.lengths().tolist() == [120] * n
+
+
+def test_timing_never_enters_a_capture(engine, monkeypatch):
+    """With MSHA_PARTS_TIMING=1 a write and a sum on a capturing stream are not timed: no
+    event is recorded or waited for inside the capture (that would invalidate it), the
+    captured calls report 0 ms, and each replay appends what the arena holds by then."""
+    import torch
+    rng = np.random.default_rng(73)
+    n = 300
+    rows_bytes = [[rng.bytes(int(x)) for x in rng.integers(0, 70, int(rng.integers(0, 4)))] for _ in range(n)]
+    arena, off, ln, begin = _packed(rows_bytes, rng)
+    d = [_dev(x) for x in (arena, off, ln, begin)]
+    out = _out(n)
+    hashes = [hashlib.sha256(b"".join(r)) for r in rows_bytes]
+
+    def want():
+        return np.frombuffer(b"".join(h.digest() for h in hashes), np.uint8).reshape(n, 32)
+
+    monkeypatch.setenv("MSHA_PARTS_TIMING", "1")
+    with DeviceStreamSet(engine, n) as s:
+        s.write_device(*d)                                              # the warm calls, timed
+        assert s.stats()["last_kernel_ms"] > 0
+        s.sum_device(out)
+        assert s.stats()["last_kernel_ms"] > 0
+        engine.device_status()
+        assert _bad_rows(out.cpu().numpy(), want()) == []
+        st = torch.cuda.Stream()
+        g = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(st):
+            g.capture_begin()
+            try:
+                s.write_device(*d, stream=st)
+                w_ms = s.stats()["last_kernel_ms"]
+                s.sum_device(out, stream=st)
+            finally:
+                g.capture_end()                                         # raises if the capture was invalidated
+        torch.cuda.synchronize()
+        assert s.stats()["launches"] == 4 and (w_ms, s.stats()["last_kernel_ms"]) == (0.0, 0.0)
+        assert s.lengths().tolist() == [len(b"".join(r)) for r in rows_bytes]   # the capture itself ran nothing
+        for _ in range(2):
+            fresh = rng.integers(0, 256, arena.size, dtype=np.uint8)
+            d[0].copy_(_dev(fresh))
+            out.zero_()
+            torch.cuda.synchronize()
+            g.replay()
+            torch.cuda.synchronize()
+            host = fresh.tobytes()
+            for i in range(n):
+                for j in range(int(begin[i]), int(begin[i + 1])):
+                    hashes[i].update(host[int(off[j]):int(off[j] + ln[j])])
+            assert _bad_rows(out.cpu().numpy(), want()) == []
+        engine.device_status()
+        del g

@@ -16,6 +16,7 @@ from mirbft_amd import _lib as L
 gpu = pytest.mark.gpu
 
 SLACK = L.MSHA_DEVICE_ARENA_SLACK
+CAPTURE_MESSAGE = "make one call of this size outside the capture first"
 
 
 def _sha(parts) -> bytes:
@@ -263,7 +264,7 @@ def test_capturable_into_a_graph(engine):
     arena, off, ln, begin = _packed(actions)
     d_arena, d_off, d_ln, d_begin = _dev(arena), _dev(off), _dev(ln), _dev(begin)
     out = torch.zeros((300, 32), dtype=torch.uint8, device="cuda:0")
-    engine.hash_actions_device(d_arena, d_off, d_ln, d_begin, out)       # the error word exists before the capture
+    engine.hash_actions_device(d_arena, d_off, d_ln, d_begin, out)
     engine.device_status()
     out.zero_()
     s = torch.cuda.Stream()
@@ -302,3 +303,106 @@ def test_parts_stats_count_calls_actions_and_launches(engine):
     assert after["launches"] - before["launches"] == 2
     assert after["last_lanes"] == 70
     assert after["last_kernel_ms"] == 0.0       # measured only under MSHA_PARTS_TIMING=1
+
+
+def _timed_call(engine, actions):
+    """One call over `actions`, its digests checked; the counters it moved and its last_kernel_ms."""
+    before = engine.parts_stats()
+    assert _bad_rows(_run(engine, *_packed(actions)), _want(actions)) == []
+    after = engine.parts_stats()
+    assert [after[k] - before[k] for k in ("calls", "actions", "launches")] == [1, len(actions), 1]
+    assert after["last_lanes"] == len(actions)
+    return after["last_kernel_ms"]
+
+
+@gpu
+def test_timing_is_read_at_each_call(engine, monkeypatch):
+    """MSHA_PARTS_TIMING is read by every call, not once in the process: off, on and off
+    again inside one process, the digests and the other counters the same each time."""
+    rng = np.random.default_rng(0x71)
+    actions = [[rng.bytes(40), rng.bytes(41)] for _ in range(70)]
+    monkeypatch.delenv("MSHA_PARTS_TIMING", raising=False)
+    assert _timed_call(engine, actions) == 0.0
+    monkeypatch.setenv("MSHA_PARTS_TIMING", "1")
+    assert _timed_call(engine, actions) > 0
+    monkeypatch.delenv("MSHA_PARTS_TIMING")
+    assert _timed_call(engine, actions) == 0.0
+
+
+@gpu
+def test_timing_never_enters_a_capture(engine, monkeypatch):
+    """With MSHA_PARTS_TIMING=1 a call on a capturing stream is not timed: no event is
+    recorded or waited for inside the capture (that would invalidate it), the captured
+    call reports 0 ms, and the graph replays as without the variable."""
+    import torch
+    rng = np.random.default_rng(0x72)
+    actions = [[rng.bytes(int(rng.integers(0, 90))) for _ in range(int(rng.integers(0, 5)))] for _ in range(300)]
+    arena, off, ln, begin = _packed(actions)
+    d_arena, d_off, d_ln, d_begin = _dev(arena), _dev(off), _dev(ln), _dev(begin)
+    out = torch.zeros((300, 32), dtype=torch.uint8, device="cuda:0")
+    monkeypatch.setenv("MSHA_PARTS_TIMING", "1")
+    engine.hash_actions_device(d_arena, d_off, d_ln, d_begin, out)       # the warm call, timed
+    engine.device_status()
+    assert engine.parts_stats()["last_kernel_ms"] > 0
+    assert _bad_rows(out.cpu().numpy(), _want(actions)) == []
+    out.zero_()
+    before = engine.parts_stats()
+    s = torch.cuda.Stream()
+    g = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        g.capture_begin()
+        try:
+            engine.hash_actions_device(d_arena, d_off, d_ln, d_begin, out, stream=s)
+        finally:
+            g.capture_end()                                              # raises if the capture was invalidated
+    torch.cuda.synchronize()
+    after = engine.parts_stats()
+    assert after["calls"] - before["calls"] == 1 and after["launches"] - before["launches"] == 1
+    assert after["last_lanes"] == 300 and after["last_kernel_ms"] == 0.0
+    assert not out.any()
+    for _ in range(2):
+        fresh = rng.integers(0, 256, arena.size, dtype=np.uint8)
+        d_arena.copy_(_dev(fresh))
+        out.zero_()
+        torch.cuda.synchronize()
+        g.replay()
+        torch.cuda.synchronize()
+        engine.device_status()
+        host = fresh.tobytes()
+        want = _want([[host[int(off[j]):int(off[j] + ln[j])] for j in range(int(begin[i]), int(begin[i + 1]))]
+                      for i in range(300)])
+        assert _bad_rows(out.cpu().numpy(), want) == []
+    del g
+
+
+@gpu
+def test_capture_without_a_warm_call_fails_cleanly():
+    """A fresh context has no error word and may not allocate one while the stream is
+    being captured: MSHA_ERR_INVALID_ARG and the documented message, the capture ends
+    empty, and the same call outside capture then works."""
+    import torch
+    from mirbft_amd import Engine
+    rng = np.random.default_rng(0x6C)
+    actions = [[rng.bytes(40), rng.bytes(41)] for _ in range(70)]
+    arena, off, ln, begin = _packed(actions)
+    d = [_dev(x) for x in (arena, off, ln, begin)]
+    out = torch.zeros((70, 32), dtype=torch.uint8, device="cuda:0")
+    with Engine(1) as eng:
+        s = torch.cuda.Stream()
+        g = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s):
+            g.capture_begin()
+            try:
+                with pytest.raises(MshaError) as ei:
+                    eng.hash_actions_device(*d, out, stream=s)
+            finally:
+                g.capture_end()
+        torch.cuda.synchronize()
+        assert ei.value.code == L.MSHA_ERR_INVALID_ARG and CAPTURE_MESSAGE in str(ei.value)
+        assert "msha_hash_actions_device" in str(ei.value)
+        assert not out.any() and eng.parts_stats()["calls"] == 0
+        eng.hash_actions_device(*d, out)
+        eng.device_status()
+        assert _bad_rows(out.cpu().numpy(), _want(actions)) == []

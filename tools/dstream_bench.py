@@ -208,7 +208,7 @@ def main() -> int:
     if a.reps < 5:
         ap.error("at least 5 repetitions")
     if a.measure == "kernel":
-        os.environ["MSHA_PARTS_TIMING"] = "1"      # read once, at the library's first device call
+        os.environ["MSHA_PARTS_TIMING"] = "1"      # read by the library at each call
     elif os.environ.get("MSHA_PARTS_TIMING") == "1":
         ap.error("recorder measures enqueue-only calls: unset MSHA_PARTS_TIMING")
     from mirbft_amd import _lib
