@@ -688,6 +688,115 @@ typedef struct {
 int msha_get_concat_stats(const msha_ctx* ctx, msha_concat_stats* out);
 
 /*
+ * Part lists with their long lists routed to the chains (ABI 10, additive:
+ * MSHA_HAS_PARTS_ROUTED tells a build that has it). ProcessHashActions from HBM
+ * (serial.go:180-198) once more, for batches in which a few lists are very long: an
+ * EpochChange's Data (stateless.go:323-352) is thousands of parts, and as a lane of
+ * msha_hash_actions_device_planned it holds its whole call up. This entry is that one
+ * with the decision made on the GPU inside the call: it finds the long lists among the
+ * named ones, flattens them as msha_concat_lists_device does and hashes them on the
+ * eight-lane chain kernel, and hashes the rest as lanes. One call, and the caller need
+ * not know which lists are long.
+ *
+ * SAME DIGESTS, SAME ERRORS as msha_hash_actions_device_planned. Lists, actions, d_out,
+ * the READ CONTRACT and FOLDING (a named list is hashed exactly once; a list no action
+ * names is never read) are that entry's, and so are both device error bits: bit 8 for a
+ * d_action_list entry >= n_lists, bit 4 for a list whose part range decreases or spans
+ * 2^32 parts or more, all-zero digests for either. Checked on the host
+ * (MSHA_ERR_INVALID_ARG, each with a text): null pointers, d_arena's alignment, the two
+ * counts' bound, n_actions != n_lists without d_action_list, and the bounds of `opts`
+ * below. n_actions == 0 returns MSHA_OK and launches nothing; it is looked at after the
+ * counts and before `opts` and the pointers, which such a call does not use. Routing is
+ * an optimisation: no input makes a digest differ from the planned entry's, and nothing
+ * here raises bit 16 (msha_concat_lists_device's).
+ *
+ * WHAT IS ROUTED. A list is LONG when some action names it, its part range is valid and
+ * msha_blocks_for_len(the sum of its part lengths) >= long_blocks. A long list that
+ * finds a slot and room is routed: its parts are written back to back, from a
+ * MSHA_DEVICE_ALIGN-aligned start and with a zeroed pad, into a flatten buffer the
+ * context owns, and it is hashed from there by the eight-lane chain kernel; it is not a
+ * lane of the parts kernel. msha_set_kernel_policy does not apply: the routed lists
+ * always run on that kernel, 16 lists a compute unit, which is why max_long is capped.
+ *
+ * CAPS NEVER FAIL A CALL. At most max_long lists are routed, and a list is given room
+ * only while off + round16(len) + MSHA_DEVICE_ARENA_SLACK <= long_bytes holds for it
+ * (off: the rounded lengths of the lists given room before it). A long list that finds
+ * no slot or no room stays an ordinary lane and its digest is as right as any. When
+ * every long list fits both caps, exactly the long lists are routed. When not all fit,
+ * which of them are routed is unspecified, but of long lists of one length L exactly
+ * min(n_long, max_long, floor((long_bytes - MSHA_DEVICE_ARENA_SLACK) / round16(L)))
+ * are.
+ *
+ * DEFAULTS (a zero field, or opts NULL). long_blocks: 64, the threshold with the lowest
+ * storm median in tools/parts_route_bench.py's sweep (profiles/parts_routed/README.md).
+ * max_long: 16 x the device's compute units. long_bytes: 32 MiB, seven times the 4.76 MB
+ * of that benchmark's pool of 100 EpochChange lists, which its storm names too. When no
+ * list is long the call is the planned one plus two launches that find nothing to do:
+ * on 2^20 one-part lists the two calls differ by less than their spread (the same file).
+ *
+ * ORDER: the lanes that remain are in descending block-count class, as in
+ * msha_hash_actions_device_planned.
+ *
+ * ONE STREAM, capturable: the kernels (init, mark, measure, scan, scatter, copy, chain,
+ * hash, fill) all go on `stream` (NULL: the context's own); there is no memset, no
+ * library stream and no host wait. The workspace -- the planned entry's arrays, five
+ * words a slot and the flatten buffer -- is this entry's own allocation in the context,
+ * so calls of this and of the planned entry on one context share no memory. It grows by
+ * hipMalloc only while `stream` is NOT being captured, and growing waits for the
+ * previous routed call; on a capturing stream with too small a workspace (or a context
+ * that has made no device call yet) the call fails with MSHA_ERR_INVALID_ARG and says
+ * to make one call of that size outside the capture first. Outside capture a call is
+ * ordered after the previous routed call of the context through a library event. A
+ * captured call holds the workspace's addresses, as a captured planned call does.
+ *
+ * MSHA_PARTS_TIMING and MSHA_PARTS_PLAN_WAVE_SUM apply as in the planned entry.
+ */
+#define MSHA_HAS_PARTS_ROUTED 1
+typedef struct {
+  uint32_t long_blocks;  /* a named, valid list of >= this many 64-byte blocks is LONG; 0: the default */
+  uint32_t max_long;     /* at most this many lists are routed per call; 0: 16 x CUs; above 16 x CUs: INVALID_ARG */
+  uint64_t long_bytes;   /* bytes of the context's flatten buffer; 0: the default; below 16 + MSHA_DEVICE_ARENA_SLACK
+                            or above 2^48: INVALID_ARG */
+} msha_route_opts;       /* NULL: all defaults */
+#define MSHA_ROUTE_LONG_BLOCKS_DEFAULT 64u
+#define MSHA_ROUTE_LONG_BYTES_DEFAULT (32ull << 20)
+int msha_hash_actions_device_routed(msha_ctx* ctx, const uint8_t* d_arena,
+                                    const uint64_t* d_part_off, const uint64_t* d_part_len,
+                                    const uint64_t* d_list_part_begin, uint64_t n_lists,
+                                    const uint32_t* d_action_list, uint64_t n_actions,
+                                    const msha_route_opts* opts, uint8_t* d_out, void* stream);
+/* Counters of msha_hash_actions_device_routed (msha_parts_stats, msha_parts_plan_stats
+ * and msha_concat_stats are untouched by it; its chain launch counts in msha_stats as
+ * every chain launch does: launches_coop and launches_chain8). */
+typedef struct {
+  uint64_t calls;             /* calls that enqueued their launches */
+  uint64_t actions;           /* digests they produce */
+  uint64_t lists;             /* lists they were given */
+  uint64_t launches_plan;     /* init, mark, measure, scan and scatter launches */
+  uint64_t launches_copy;     /* k_concat_copy launches: one a call */
+  uint64_t launches_chain;    /* eight-lane chain launches: one a call */
+  uint64_t launches_hash;     /* k_digest_parts_planned launches */
+  uint64_t launches_fill;     /* k_parts_fill launches (calls with d_action_list) */
+  uint64_t last_lanes;        /* the last call's lists hashed as lanes, ... */
+  uint64_t last_blocks;       /* ... the 64-byte blocks compressed for those, ... */
+  uint64_t last_routed;       /* ... its routed lists and ... */
+  uint64_t last_routed_bytes; /* ... the bytes of the flatten buffer they were given; all read back, and */
+  double last_kernel_ms;      /* the call's kernels timed by HIP events, only under MSHA_PARTS_TIMING=1
+                                 (read at each call; the call then waits for its kernels; never while
+                                 `stream` is being captured); otherwise these five are 0 */
+} msha_parts_route_stats;
+int msha_get_parts_route_stats(const msha_ctx* ctx, msha_parts_route_stats* out);
+/* Diagnostic, synchronous, like msha_parts_plan_read_order: waits for the device, then
+ * copies the last routed call's routed list ids (in no particular order) into
+ * lists[0 .. min(cap, *n_routed)), their count into *n_routed and the bytes of the
+ * flatten buffer they were given into *routed_bytes. lists may be NULL when cap is 0. */
+int msha_parts_route_read(msha_ctx* ctx, uint32_t* lists, uint64_t cap, uint64_t* n_routed,
+                          uint64_t* routed_bytes);
+/* The same for the lanes that remained: the last routed call's lane order, as
+ * msha_parts_plan_read_order gives the planned entry's. */
+int msha_parts_route_read_order(msha_ctx* ctx, uint32_t* order, uint64_t cap, uint64_t* lanes);
+
+/*
  * Host-only helpers (no GPU needed).
  * msha_blocks_for_len: number of 64-byte compressions for an L-byte message,
  *   floor(L/64) + (L%64 < 56 ? 1 : 2)  (FIPS 180-4 5.1.1 padding).

@@ -34,6 +34,9 @@ MSHA_KERNEL_COOP = 2
 MSHA_STREAM_STATE_BYTES = 108
 MSHA_PARTS_FOLD = 1
 MSHA_HAS_PARTS_CONCAT = 1
+MSHA_HAS_PARTS_ROUTED = 1
+MSHA_ROUTE_LONG_BLOCKS_DEFAULT = 64
+MSHA_ROUTE_LONG_BYTES_DEFAULT = 32 << 20
 MSHA_HAS_STREAMS_DEVICE = 1
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -155,6 +158,32 @@ class MshaConcatStats(ctypes.Structure):
     ]
 
 
+class MshaRouteOpts(ctypes.Structure):
+    _fields_ = [
+        ("long_blocks", ctypes.c_uint32),
+        ("max_long", ctypes.c_uint32),
+        ("long_bytes", ctypes.c_uint64),
+    ]
+
+
+class MshaPartsRouteStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", ctypes.c_uint64),
+        ("actions", ctypes.c_uint64),
+        ("lists", ctypes.c_uint64),
+        ("launches_plan", ctypes.c_uint64),
+        ("launches_copy", ctypes.c_uint64),
+        ("launches_chain", ctypes.c_uint64),
+        ("launches_hash", ctypes.c_uint64),
+        ("launches_fill", ctypes.c_uint64),
+        ("last_lanes", ctypes.c_uint64),
+        ("last_blocks", ctypes.c_uint64),
+        ("last_routed", ctypes.c_uint64),
+        ("last_routed_bytes", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
 class MshaDstreamsStats(ctypes.Structure):
     _fields_ = [
         ("writes", ctypes.c_uint64),
@@ -238,6 +267,13 @@ SIGNATURES = {
                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "msha_get_concat_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaConcatStats)]),
+    "msha_hash_actions_device_routed": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                       ctypes.c_uint64, ctypes.POINTER(MshaRouteOpts),
+                                                       ctypes.c_void_p, ctypes.c_void_p]),
+    "msha_get_parts_route_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaPartsRouteStats)]),
+    "msha_parts_route_read": (ctypes.c_int, [_ctxp, _u32p, ctypes.c_uint64, _u64p, _u64p]),
+    "msha_parts_route_read_order": (ctypes.c_int, [_ctxp, _u32p, ctypes.c_uint64, _u64p]),
     "msha_dstreams_create": (ctypes.c_int, [_ctxp, ctypes.c_uint64, ctypes.POINTER(_setp)]),
     "msha_dstreams_destroy": (None, [_setp]),
     "msha_dstreams_write_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -300,6 +336,7 @@ _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mi
               "streams.cpp",
               "parts_gather.hpp", "parts_kernels.hip", "parts.cpp",
               "parts_digest.hpp", "parts_plan.hpp", "parts_plan.hip", "parts_plan.cpp",
+              "parts_route.hpp", "parts_route.cpp",
               "stream_device.hpp", "stream_device.hip", "stream_device.cpp",
               "parts_concat.hpp", "parts_concat.hip", "parts_concat.cpp")
 

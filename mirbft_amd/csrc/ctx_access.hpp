@@ -1,7 +1,8 @@
 // What a translation unit outside mirsha.cpp may reach of a context (msha_ctx is
 // defined there): its lock, its first device, its error text and what the device
 // entries keep in it. Defined at the end of mirsha.cpp; used, through host_call.hpp, by
-// streams.cpp, parts.cpp, parts_plan.cpp, parts_concat.cpp and stream_device.cpp.
+// streams.cpp, parts.cpp, parts_plan.cpp, parts_concat.cpp, parts_route.cpp and
+// stream_device.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -56,6 +57,38 @@ struct PartsPlanState {
 };
 // Call with the lock held.
 PartsPlanState& ctx_parts_plan(msha_ctx* ctx);
+
+// What msha_hash_actions_device_routed (parts_route.cpp) keeps in the context: a
+// workspace of its own (the planned call's arrays, the route's slots and the flatten
+// buffer in one allocation on the first device: a planned and a routed call share no
+// memory), the event that orders a call after the previous one's use of it, where the
+// last call's arrays lie in it (msha_parts_route_read*) and its counters. Freed by
+// msha_ctx_destroy.
+struct PartsRouteState {
+  void* ws = nullptr;
+  uint64_t ws_bytes = 0;
+  hipEvent_t last = nullptr;  // recorded after each call outside capture
+  bool ran = false;           // some call has filled the workspace
+  uint64_t last_lists = 0, last_slots = 0;               // n_lists and max_long of the last call
+  uint64_t at_order = 0, at_chain = 0, at_out_idx = 0, at_claim = 0;  // byte offsets in ws of its arrays
+  msha_parts_route_stats stats{};
+  void release() {
+    if (last) {
+      (void)hipEventSynchronize(last);
+      (void)hipEventDestroy(last);
+    }
+    if (ws) (void)hipFree(ws);
+    ws = nullptr;
+    last = nullptr;
+    ws_bytes = 0;
+  }
+};
+// Call with the lock held.
+PartsRouteState& ctx_parts_route(msha_ctx* ctx);
+// Counts a launch_digest_batch launch of a device entry in msha_stats (the routed
+// entry's chain: launches_coop and launches_chain8), as mirsha.cpp's own device entries
+// count theirs. kind: the kernels.hpp LaunchKind the launcher reported.
+void ctx_count_launch(msha_ctx* ctx, int kind);
 // Has a device call already allocated the first device's error word? Until then
 // ctx_first_device allocates, which a capturing stream does not allow.
 bool ctx_first_device_ready(const msha_ctx* ctx);

@@ -370,6 +370,27 @@ hipError_t launch_digest_parts_planned(const PartsPlanArgs& a, hipStream_t st);
 // (with action_list) out[i] = table[action_list[i]], zeros for an entry out of range.
 hipError_t launch_parts_fill(const PartsPlanArgs& a, hipStream_t st);
 
+// The planned call with its long lists routed to the eight-lane chain (parts_plan.hip
+// k_route_init / k_route_measure, msha_hash_actions_device_routed): what the routing adds
+// to PartsPlanArgs. A routed list l holds a slot s < max_long: sel[s] = l, its bytes go
+// to flat + msg_off[s] (msg_len[s] of them, parts_concat.hip k_concat_copy over
+// sel / msg_off / msg_len), and lane s of the chain launch (order = chain_order,
+// out_idx) hashes them into row l. Claim rules and the unfilled slot: parts_route.hpp.
+struct RouteArgs {
+  uint32_t long_blocks = 0;  // >= 1
+  uint32_t max_long = 0;     // slots
+  uint64_t long_bytes = 0;   // bytes of the flatten buffer
+  uint32_t* sel = nullptr;          // max_long
+  uint64_t* msg_off = nullptr;      // max_long
+  uint64_t* msg_len = nullptr;      // max_long
+  uint32_t* chain_order = nullptr;  // max_long: slot s -> s, kNoLane when unfilled
+  uint32_t* out_idx = nullptr;      // max_long: slot s -> its list
+  unsigned long long* claim = nullptr;  // parts_route::kClaimWords counters
+};
+// init (resets the planned workspace and the route's arrays), mark (with action_list),
+// route measure, scan, scatter; *launches = how many kernels that was.
+hipError_t launch_parts_route_plan(const PartsPlanArgs& a, const RouteArgs& r, hipStream_t st, uint32_t* launches);
+
 // Part lists flattened into contiguous messages (parts_concat.hip,
 // msha_concat_lists_device). Message k is list select[k] (null: list k); its parts go
 // back to back to dst + msg_off[k], msg_off a running sum of round16(msg_len). Three

@@ -531,6 +531,7 @@ struct msha_ctx {
   msha_parts_stats parts_stats{};  // msha_hash_actions_device (msha_get_parts_stats)
   msha::PartsPlanState parts_plan;  // msha_hash_actions_device_planned (parts_plan.cpp)
   msha_concat_stats concat_stats{};  // msha_concat_lists_device (parts_concat.cpp)
+  msha::PartsRouteState parts_route;  // msha_hash_actions_device_routed (parts_route.cpp)
   // allocations handed out by msha_pinned_alloc: (pointer, mapped bytes), 0 =
   // hipHostMalloc, else an mmap striped over NUMA nodes and hipHostRegister'ed
   std::vector<std::pair<void*, uint64_t>> pinned;
@@ -2590,7 +2591,10 @@ void msha_ctx_destroy(msha_ctx* ctx) {
     (void)hipSetDevice(d.id);
     for (hipStream_t st : {d.stream, d.copy_stream, d.d2h_stream})
       if (st) (void)hipStreamSynchronize(st);
-    if (&d == &ctx->devs[0]) ctx->parts_plan.release();  // its workspace lives on the first device
+    if (&d == &ctx->devs[0]) {  // their workspaces live on the first device
+      ctx->parts_plan.release();
+      ctx->parts_route.release();
+    }
     d.release();
   }
   for (const auto& a : ctx->pinned) pinned_release(a);
@@ -3300,6 +3304,10 @@ msha_parts_stats& ctx_parts_stats(msha_ctx* ctx) { return ctx->parts_stats; }
 msha_concat_stats& ctx_concat_stats(msha_ctx* ctx) { return ctx->concat_stats; }
 
 PartsPlanState& ctx_parts_plan(msha_ctx* ctx) { return ctx->parts_plan; }
+
+PartsRouteState& ctx_parts_route(msha_ctx* ctx) { return ctx->parts_route; }
+
+void ctx_count_launch(msha_ctx* ctx, int kind) { count_launch(ctx, nullptr, static_cast<LaunchKind>(kind)); }
 
 bool ctx_first_device_ready(const msha_ctx* ctx) { return !ctx->devs.empty() && ctx->devs[0].err.p != nullptr; }
 

@@ -32,12 +32,19 @@
 // the global counters once per key the workgroup saw. A wave whose lanes all hold one
 // key (uniform batches; most waves of a sorted or clustered one) adds its population
 // count with one LDS atomic instead of 64 on one address (hist_add).
+//
+// msha_hash_actions_device_routed runs the same sequence with two kernels of its own in
+// place of the first and the third (launch_parts_route_plan): k_route_init also resets
+// the route's slots, and k_route_measure, which has the lengths in hand, decides which
+// lists leave the lanes for the eight-lane chain (parts_route.hpp). The host then puts
+// k_concat_copy and the chain launch between the scatter and k_digest_parts_planned.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "kernels.hpp"
 #include "parts_digest.hpp"
 #include "parts_plan.hpp"
+#include "parts_route.hpp"
 
 namespace msha {
 
@@ -220,9 +227,122 @@ __global__ __launch_bounds__(256) void k_parts_fill(PartsPlanArgs a) {
   dst[1] = x1;
 }
 
+// msha_hash_actions_device_routed: k_parts_init's reset plus the route's arrays -- every
+// slot back to unfilled, the claim counters to 0 -- so a call leaves nothing for the next.
+__global__ __launch_bounds__(256) void k_route_init(PartsPlanArgs a, RouteArgs r) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 16 + kKeys) a.info[i] = 0;
+  if (i < a.n_lists) a.order[i] = kNoLane;
+  if (a.used && i < (a.n_lists + 3) / 4) reinterpret_cast<uint32_t*>(a.used)[i] = 0;
+  if (i < r.max_long) {
+    r.sel[i] = 0;
+    r.msg_off[i] = 0;
+    r.msg_len[i] = parts_route::kUnfilledLen;
+    r.chain_order[i] = parts_route::kUnfilledOrder;
+    r.out_idx[i] = 0;
+  }
+  if (i < parts_route::kClaimWords) r.claim[i] = 0;
+}
+
+// k_parts_measure with the routing decision: a valid list of long_blocks blocks or more
+// claims a slot and room (parts_route.hpp). With both it is the chain's -- its slot
+// filled, its key kNoKey, out of the histogram and the block sum -- and otherwise it is
+// a lane as every other list is. The claim is settled before hist_add, whose `valid` is
+// per lane while its one-atomic path is per wave: a list counts there once or not at all.
+__global__ __launch_bounds__(256) void k_route_measure(PartsPlanArgs a, RouteArgs r) {
+  __shared__ uint32_t hist[kKeys];
+  __shared__ unsigned long long bsum;
+  for (uint32_t k = threadIdx.x; k < kKeys; k += blockDim.x) hist[k] = 0;
+  if (threadIdx.x == 0) bsum = 0;
+  __syncthreads();
+
+  const uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool named = l < a.n_lists && (!a.used || a.used[l] != 0);
+  uint64_t j0 = 0, np = 0;
+  bool bad = false;
+  if (named) {
+    j0 = a.begin[l];
+    const uint64_t jend = a.begin[l + 1];
+    bad = jend < j0 || jend - j0 > 0xffffffffull;
+    np = bad ? 0 : jend - j0;
+  }
+  const bool wide = named && np >= a.wave_sum_parts;
+  uint64_t total = 0;
+  if (named && !wide)
+    for (uint64_t j = 0; j < np; ++j) total += a.part_len[j0 + j];
+  uint64_t pending = __ballot(wide);
+  while (pending) {
+    const int lead = __ffsll((unsigned long long)pending) - 1;
+    pending &= pending - 1;
+    const uint64_t wj0 = __shfl((unsigned long long)j0, lead), wnp = __shfl((unsigned long long)np, lead);
+    uint64_t s = 0;
+    for (uint64_t j = wave_lane(); j < wnp; j += 64) s += a.part_len[wj0 + j];
+    s = wave_sum(s);
+    if ((int)wave_lane() == lead) total = s;
+  }
+  uint64_t blocks = (named && !bad) ? parts_plan::blocks_for_len(total) : 0;
+
+  bool routed = false;
+  uint64_t next = 0;
+  if (named && !bad && parts_route::is_long(blocks, r.long_blocks) &&
+      parts_route::room_ok(0, total, r.long_bytes, kArenaSlack, &next)) {  // (could it ever fit?)
+    const uint64_t ticket = atomicAdd(&r.claim[parts_route::kClaimSlots], 1ull);
+    if (parts_route::slot_ok(ticket, r.max_long)) {
+      unsigned long long* const given = &r.claim[parts_route::kClaimBytes];
+      uint64_t cur = __atomic_load_n(given, __ATOMIC_RELAXED);
+      while (parts_route::room_ok(cur, total, r.long_bytes, kArenaSlack, &next)) {
+        const uint64_t seen = atomicCAS(given, (unsigned long long)cur, (unsigned long long)next);
+        if (seen == cur) {
+          routed = true;
+          break;
+        }
+        cur = seen;
+      }
+      if (routed) {
+        const uint32_t s = (uint32_t)ticket;
+        r.sel[s] = (uint32_t)l;
+        r.msg_off[s] = cur;
+        r.msg_len[s] = total;
+        r.chain_order[s] = s;
+        r.out_idx[s] = (uint32_t)l;
+        atomicAdd(&r.claim[parts_route::kClaimRouted], 1ull);
+      }
+    }
+  }
+  const bool lane = named && !routed;
+  if (routed) blocks = 0;
+  const uint32_t key = lane ? parts_plan::class_key(blocks) : kNoKey;
+  if (l < a.n_lists) a.key16[l] = (uint16_t)key;
+  (void)hist_add(hist, key, lane);
+  const uint64_t wblocks = wave_sum(blocks);
+  if (wave_lane() == 0 && wblocks) atomicAdd(&bsum, (unsigned long long)wblocks);
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < kKeys; k += blockDim.x) {
+    const uint32_t c = hist[k];
+    if (c) atomicAdd(&a.cnt[k], c);
+  }
+  if (threadIdx.x == 0 && bsum) atomicAdd(reinterpret_cast<unsigned long long*>(a.info + 2), bsum);
+}
+
 unsigned grid256(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
+
+hipError_t launch_parts_route_plan(const PartsPlanArgs& a, const RouteArgs& r, hipStream_t st, uint32_t* launches) {
+  uint32_t k = 1;
+  uint64_t words = a.n_lists > 16 + kKeys ? a.n_lists : 16 + kKeys;
+  if (r.max_long > words) words = r.max_long;
+  hipLaunchKernelGGL(k_route_init, dim3(grid256(words)), dim3(256), 0, st, a, r);
+  if (a.action_list) {
+    hipLaunchKernelGGL(k_parts_mark, dim3(grid256(a.n_actions)), dim3(256), 0, st, a);
+    ++k;
+  }
+  hipLaunchKernelGGL(k_route_measure, dim3(grid256(a.n_lists)), dim3(256), 0, st, a, r);
+  hipLaunchKernelGGL(k_parts_scan, dim3(1), dim3(kScanThreads), 0, st, a);
+  hipLaunchKernelGGL(k_parts_scatter, dim3(grid256(a.n_lists)), dim3(256), 0, st, a);
+  if (launches) *launches = k + 3;
+  return hipGetLastError();
+}
 
 hipError_t launch_parts_plan(const PartsPlanArgs& a, hipStream_t st, uint32_t* launches) {
   uint32_t k = 1;

@@ -395,6 +395,78 @@ class Engine:
                                                              ctypes.byref(lanes)))
         return order[:lanes.value]
 
+    def hash_actions_device_routed(self, arena, part_off, part_len, list_begin, out, action_list=None,
+                                   stream=None, long_blocks: int = 0, max_long: int = 0,
+                                   long_bytes: int = 0) -> None:
+        """msha_hash_actions_device_routed: hash_actions_device_planned with the long
+        lists found on the GPU inside the call, flattened into a buffer of the context's
+        and hashed by the eight-lane chain kernel; the others run as lanes. A named list
+        of long_blocks 64-byte blocks or more is long; at most max_long lists and
+        long_bytes bytes are routed, and what finds no slot or no room stays a lane. 0
+        takes a default (64 blocks, 16 x compute units, 32 MiB). Digests, errors and
+        arena rules are hash_actions_device_planned's."""
+        n = out.numel() // 32 if hasattr(out, "numel") else 0      # out is n x 32 bytes
+        self._check_device_args(n, out, arena=arena, part_off=part_off, part_len=part_len,
+                                list_begin=list_begin, action_list=action_list)
+        if out.numel() != 32 * n:
+            raise ValueError(f"out holds {out.numel()} bytes, not a multiple of 32")
+        n_lists = list_begin.numel() - 1
+        if n_lists < 0:
+            raise ValueError("list_begin must have at least one entry")
+        if action_list is None and n_lists != n:
+            raise ValueError(f"list_begin has {list_begin.numel()} entries, expected {n + 1} (out holds {n} digests "
+                             "and there is no action_list)")
+        if part_len.numel() != part_off.numel():
+            raise ValueError(f"part_len has {part_len.numel()} entries, part_off {part_off.numel()}")
+        if arena.data_ptr() % L.MSHA_DEVICE_ALIGN:
+            raise ValueError(f"arena must start on a {L.MSHA_DEVICE_ALIGN}-byte boundary")
+        for name, v, top in (("long_blocks", long_blocks, 1 << 32), ("max_long", max_long, 1 << 32),
+                             ("long_bytes", long_bytes, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise ValueError(f"{name} must be in [0, 2^{top.bit_length() - 1})")
+        opts = L.MshaRouteOpts(int(long_blocks), int(max_long), int(long_bytes))
+        if arena.numel() == 0 and n:    # nothing to read: an empty tensor has no address to pass
+            arena = list_begin.new_zeros(2)
+        if part_off.numel() == 0 and n:  # every list has zero parts
+            part_off = part_len = list_begin.new_zeros(2)
+        # (n == 0 goes to the library too, which launches nothing)
+        self._check(self._lib.msha_hash_actions_device_routed(
+            self._ctx, arena.data_ptr(), part_off.data_ptr(), part_len.data_ptr(), list_begin.data_ptr(), n_lists,
+            None if action_list is None else action_list.data_ptr(), n, ctypes.byref(opts), out.data_ptr(),
+            self._stream_ptr(stream)))
+
+    def parts_route_stats(self) -> dict:
+        """msha_get_parts_route_stats: calls, actions, lists and launches of
+        hash_actions_device_routed and, under MSHA_PARTS_TIMING=1, the last call's lanes,
+        their blocks, its routed lists, their bytes and the kernel time."""
+        s = L.MshaPartsRouteStats()
+        self._check(self._lib.msha_get_parts_route_stats(self._ctx, ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in L.MshaPartsRouteStats._fields_}
+
+    def parts_route_lists(self):
+        """msha_parts_route_read: (ids, bytes) of the last hash_actions_device_routed call
+        -- the lists it routed, in no particular order, and the bytes of the flatten
+        buffer they were given. Waits for the device; a diagnostic."""
+        n, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self._lib.msha_parts_route_read(self._ctx, None, 0, ctypes.byref(n), ctypes.byref(b)))
+        ids = np.empty(n.value, dtype=np.uint32)
+        if n.value:
+            self._check(self._lib.msha_parts_route_read(self._ctx, _p(ids, ctypes.c_uint32), ids.size,
+                                                        ctypes.byref(n), ctypes.byref(b)))
+        return ids[:n.value], int(b.value)
+
+    def parts_route_order(self) -> np.ndarray:
+        """msha_parts_route_read_order: the lane order of the last
+        hash_actions_device_routed call (the lists that stayed lanes, first lane first).
+        Waits for the device; a diagnostic."""
+        lanes = ctypes.c_uint64(0)
+        self._check(self._lib.msha_parts_route_read_order(self._ctx, None, 0, ctypes.byref(lanes)))
+        order = np.empty(lanes.value, dtype=np.uint32)
+        if lanes.value:
+            self._check(self._lib.msha_parts_route_read_order(self._ctx, _p(order, ctypes.c_uint32), order.size,
+                                                              ctypes.byref(lanes)))
+        return order[:lanes.value]
+
     def concat_lists_device(self, arena, part_off, part_len, list_begin, dst, msg_off, msg_len, select=None,
                             stream=None) -> None:
         """msha_concat_lists_device: message k is list select[k] (select None: list k),
