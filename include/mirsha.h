@@ -400,6 +400,7 @@ int msha_finish_device(msha_ctx* ctx, const uint32_t* d_state, const uint64_t* d
  * returns after enqueueing exactly one kernel launch -- no memset, no library stream,
  * no event wait, no allocation -- so it captures into a HIP graph as one kernel node
  * (a replayed write appends again). n_rows == 0 returns MSHA_OK and launches nothing.
+ * (msha_dstreams_write_jobs_device, further down, is the exception: several launches.)
  * Ordering between calls on different HIP streams is the caller's. A set must be
  * destroyed before its context; calls on it take the context's lock.
  *
@@ -475,6 +476,70 @@ typedef struct {
                              captured); otherwise 0 and the call stays enqueue-only */
 } msha_dstreams_stats;
 int msha_dstreams_get_stats(const msha_dstreams* set, msha_dstreams_stats* out);
+
+/*
+ * Write jobs in call order: msha_streams_write's job list in device memory (ABI 10,
+ * additive: MSHA_HAS_STREAMS_DEVICE_JOBS tells a build that has it). NodeState.Apply
+ * (recorder.go:333-359) makes its Write calls in commit order, every node every
+ * digest as it arrives; a caller that learns on the device which stream takes which
+ * chunk holds that order, not the CSR grouped by stream that
+ * msha_dstreams_write_device wants. Here, for j = 0 .. n_jobs-1 in that order,
+ *   stream d_job_stream[j] appends d_arena[d_job_off[j] : d_job_off[j] + d_job_len[j]].
+ * A stream may be named any number of times; its chunks append in job order; empty
+ * chunks contribute nothing. The result is bit for bit what msha_dstreams_write_device
+ * produces for the same jobs grouped stably by stream: state, buffer and length.
+ *
+ * The grouping is done on the GPU inside the call: a stable radix sort of (min(stream,
+ * n), j), 8 bits a pass, ceil(bit_width(n) / 8) passes of three kernels each, two
+ * kernels that turn the order into the CSR, then msha_dstreams_write_device's kernel
+ * over all n streams. So, UNLIKE the four device calls above, this one enqueues
+ * SEVERAL kernel launches, 3 * passes + 3, all of them on `stream` (NULL: the
+ * context's own), still with no memset, no library stream and no host wait; it
+ * captures into a HIP graph as a chain of kernel nodes (a replay appends again). No
+ * kernel waits on another workgroup. n_jobs == 0 returns MSHA_OK and launches nothing.
+ *
+ * The arena rules are msha_dstreams_write_device's (the READ CONTRACT of
+ * msha_hash_actions_device): any start, 16-byte aligned d_arena,
+ * MSHA_DEVICE_ARENA_SLACK readable bytes behind the last chunk, offsets below 2^63.
+ * d_job_off[j] and d_job_len[j] are read for every job; arena bytes only for valid
+ * jobs. A job whose stream is >= n is DROPPED: no stream is touched by it, its chunk is
+ * not read, every other job of the call is applied exactly, and msha_device_status()
+ * reports msha_dstreams_*'s row out of range (bit 32), once. Checked on the host
+ * (MSHA_ERR_INVALID_ARG with a text, no stream changed): null pointers, d_arena's
+ * alignment, n_jobs >= 2^32 - 1.
+ *
+ * The workspace (about 32.5 bytes a job and 8 (n + 1)) belongs to the set and is freed
+ * in destroy. It grows, by hipMalloc, only while `stream` is not being captured, after
+ * waiting for the set's previous jobs call; on a capturing stream a workspace that is
+ * too small is MSHA_ERR_INVALID_ARG: make one call of that size outside the capture
+ * first. Outside capture a call is ordered after the set's previous jobs call through
+ * an event, so two HIP streams do not race on the workspace; ordering against the
+ * set's other calls is the caller's, as above.
+ */
+#define MSHA_HAS_STREAMS_DEVICE_JOBS 1
+int msha_dstreams_write_jobs_device(msha_dstreams* set, const uint8_t* d_arena,
+                                    const uint32_t* d_job_stream, const uint64_t* d_job_off,
+                                    const uint64_t* d_job_len, uint64_t n_jobs, void* stream);
+typedef struct {
+  uint64_t calls;           /* jobs calls that enqueued their launches (msha_dstreams_stats counts none of them) */
+  uint64_t jobs;            /* jobs of those calls */
+  uint64_t launches_sort;   /* histogram, scan and scatter launches: 3 a pass */
+  uint64_t launches_rows;   /* the two CSR kernels */
+  uint64_t launches_write;  /* msha_dstreams_write_device's kernel: one a call */
+  uint64_t last_passes;     /* radix passes of the last call: ceil(bit_width(n) / 8) */
+  uint64_t last_jobs;
+  uint64_t tile_jobs;       /* jobs a workgroup ranks per pass: a constant, valid from create */
+  double last_kernel_ms;    /* all of the last call's kernels by HIP events, only under MSHA_PARTS_TIMING=1
+                               (the call then waits for them; never while `stream` is being captured) */
+} msha_dstreams_jobs_stats;
+int msha_dstreams_get_jobs_stats(const msha_dstreams* set, msha_dstreams_jobs_stats* out);
+/* Diagnostic, synchronous (waits for the device): the job order of the set's last jobs
+ * call, position 0 first -- order[p] is the job applied p-th, jobs of one stream
+ * adjacent and in call order, dropped jobs last -- up to cap entries; *n_jobs = that
+ * call's job count, *n_valid = how many leading positions are valid jobs. It is
+ * argsort(min(stream, n), stable) exactly. Before any jobs call both counts are 0. */
+int msha_dstreams_jobs_read_order(msha_dstreams* set, uint32_t* order, uint64_t cap,
+                                  uint64_t* n_jobs, uint64_t* n_valid);
 
 /*
  * ProcessHashActions from HBM (serial.go:180-198), the device-resident form of

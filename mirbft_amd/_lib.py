@@ -38,6 +38,7 @@ MSHA_HAS_PARTS_ROUTED = 1
 MSHA_ROUTE_LONG_BLOCKS_DEFAULT = 64
 MSHA_ROUTE_LONG_BYTES_DEFAULT = 32 << 20
 MSHA_HAS_STREAMS_DEVICE = 1
+MSHA_HAS_STREAMS_DEVICE_JOBS = 1
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -196,6 +197,20 @@ class MshaDstreamsStats(ctypes.Structure):
     ]
 
 
+class MshaDstreamsJobsStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", ctypes.c_uint64),
+        ("jobs", ctypes.c_uint64),
+        ("launches_sort", ctypes.c_uint64),
+        ("launches_rows", ctypes.c_uint64),
+        ("launches_write", ctypes.c_uint64),
+        ("last_passes", ctypes.c_uint64),
+        ("last_jobs", ctypes.c_uint64),
+        ("tile_jobs", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
 _setp = ctypes.c_void_p
 
 # name -> (restype, argtypes)
@@ -288,6 +303,10 @@ SIGNATURES = {
     "msha_dstreams_export": (ctypes.c_int, [_setp, _u64p, ctypes.c_uint64, _u8p]),
     "msha_dstreams_import": (ctypes.c_int, [_setp, _u64p, ctypes.c_uint64, _u8p]),
     "msha_dstreams_get_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaDstreamsStats)]),
+    "msha_dstreams_write_jobs_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "msha_dstreams_get_jobs_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaDstreamsJobsStats)]),
+    "msha_dstreams_jobs_read_order": (ctypes.c_int, [_setp, _u32p, ctypes.c_uint64, _u64p, _u64p]),
 }
 
 _lib = None
@@ -337,7 +356,7 @@ _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mi
               "parts_gather.hpp", "parts_kernels.hip", "parts.cpp",
               "parts_digest.hpp", "parts_plan.hpp", "parts_plan.hip", "parts_plan.cpp",
               "parts_route.hpp", "parts_route.cpp",
-              "stream_device.hpp", "stream_device.hip", "stream_device.cpp",
+              "stream_device.hpp", "stream_device.hip", "stream_device.cpp", "stream_jobs.hpp", "stream_jobs.hip",
               "parts_concat.hpp", "parts_concat.hip", "parts_concat.cpp")
 
 

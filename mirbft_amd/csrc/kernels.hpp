@@ -325,6 +325,30 @@ hipError_t launch_dstream_rows_get(const DstreamRows& r, const uint32_t* id, uin
 hipError_t launch_dstream_rows_set(const DstreamRows& r, const uint32_t* id, uint64_t k, const uint32_t* packed,
                                    hipStream_t st);
 
+// Write jobs grouped by stream (stream_jobs.hip, msha_dstreams_write_jobs_device): the
+// n_jobs jobs (job_stream[j], job_off[j], job_len[j]) sorted stably by min(stream,
+// n_streams) in `passes` radix passes through the two pair buffers (key, job index),
+// then goff / glen = the offsets and lengths in that order and begin[t] = the first
+// position of a key >= t for t in [0, n_streams]: the CSR launch_dstream_write takes
+// with row NULL. A job whose stream is >= n_streams sorts behind begin[n_streams] and
+// sets kErrStreamRow. 3 launches a pass and 2 more, all on st; no workgroup waits on
+// another. The buffers are laid out by stream_jobs.hpp Layout.
+struct StreamJobsArgs {
+  const uint32_t* job_stream = nullptr;
+  const uint64_t* job_off = nullptr;
+  const uint64_t* job_len = nullptr;
+  uint64_t n_jobs = 0, n_streams = 0;
+  uint2* pairs[2] = {nullptr, nullptr};
+  uint64_t* goff = nullptr;
+  uint64_t* glen = nullptr;
+  uint32_t* counts = nullptr;
+  uint64_t* begin = nullptr;
+  uint32_t* err = nullptr;
+  uint32_t passes = 0;
+};
+hipError_t launch_stream_jobs(const StreamJobsArgs& a, hipStream_t st, uint32_t* sort_launches,
+                              uint32_t* row_launches);
+
 // Multi-part actions (parts_kernels.hip k_digest_parts, msha_hash_actions_device): lane
 // i hashes action a = order ? order[i] : i, the concatenation of the parts
 // [begin[a], begin[a + 1]) (part j = arena[part_off[j] : part_off[j] + part_len[j]], any

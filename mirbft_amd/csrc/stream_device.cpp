@@ -6,6 +6,12 @@
 // the kernels report the rest through the device error word (msha_device_status).
 // Length, export and import are synchronous and move whole streams through a staging
 // buffer of their own.
+//
+// msha_dstreams_write_jobs_device is the one device call of several launches: the jobs
+// are grouped by stream on the GPU (stream_jobs.hip) in a workspace the set owns, then
+// Write's kernel runs over all n streams. The workspace follows the rule of
+// msha_hash_actions_device_planned (parts_plan.cpp): it grows only outside stream
+// capture, and a call outside capture is ordered after the set's previous jobs call.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -16,13 +22,27 @@
 #include "../../include/mirsha.h"
 #include "host_call.hpp"
 #include "stream_device.hpp"
+#include "stream_jobs.hpp"
 #include "stream_state.hpp"
+
+// The workspace of the jobs calls and what msha_dstreams_jobs_read_order needs of the
+// last one.
+struct DstreamJobs {
+  void* ws = nullptr;
+  uint64_t ws_bytes = 0;
+  hipEvent_t last = nullptr;  // recorded after the last call made outside capture
+  bool ran = false;
+  uint64_t last_jobs = 0;
+  uint32_t last_passes = 0;
+  msha_dstreams_jobs_stats st{};
+};
 
 struct msha_dstreams {
   msha_ctx* ctx = nullptr;
   msha::CtxDevice dev;
   msha::DstreamRows rows;
   msha_dstreams_stats st{};
+  DstreamJobs jobs;
 };
 
 namespace {
@@ -46,6 +66,8 @@ void release(msha_dstreams* s) {
   if (s->rows.state) (void)hipFree(s->rows.state);
   if (s->rows.tail) (void)hipFree(s->rows.tail);
   if (s->rows.length) (void)hipFree(s->rows.length);
+  if (s->jobs.ws) (void)hipFree(s->jobs.ws);  // waits for the device
+  if (s->jobs.last) (void)hipEventDestroy(s->jobs.last);
 }
 
 // The row arguments every device call shares. Call with the lock held.
@@ -119,6 +141,7 @@ int msha_dstreams_create(msha_ctx* ctx, uint64_t n, msha_dstreams** out) {
   if (!s) return msha::ctx_fail(ctx, MSHA_ERR_OUT_OF_MEMORY, "host allocation failed");
   s->ctx = ctx;
   s->rows.n = n;
+  s->jobs.st.tile_jobs = msha::sjobs::kTileJobs;
   const int rc = msha::guard(ctx, [&] {
     s->dev = msha::ctx_first_device(ctx);
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->rows.state), 32 * n));
@@ -161,6 +184,120 @@ int msha_dstreams_write_device(msha_dstreams* s, const uint8_t* d_arena, const u
   return device_call(s, kEntry, kWrite, d_row, n_rows, stream, "k_dstream_write launch", [&](hipStream_t st) {
     return msha::launch_dstream_write(s->rows, d_arena, d_part_off, d_part_len, d_row_part_begin, d_row, n_rows,
                                       s->dev.err, st);
+  });
+}
+
+int msha_dstreams_write_jobs_device(msha_dstreams* s, const uint8_t* d_arena, const uint32_t* d_job_stream,
+                                    const uint64_t* d_job_off, const uint64_t* d_job_len, uint64_t n_jobs,
+                                    void* stream) {
+  static const char* const kEntry = "msha_dstreams_write_jobs_device";
+  namespace sj = msha::sjobs;
+  if (!s) return MSHA_ERR_INVALID_ARG;
+  if (n_jobs == 0) return MSHA_OK;
+  std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
+  if (!d_arena || !d_job_stream || !d_job_off || !d_job_len)
+    return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
+  if (reinterpret_cast<uintptr_t>(d_arena) % MSHA_DEVICE_ALIGN)
+    return msha::bad_arg(s->ctx, kEntry, "d_arena must be 16-byte aligned");
+  if (n_jobs >= sj::kMaxJobs) return msha::bad_arg(s->ctx, kEntry, "n_jobs must be below 2^32 - 1");
+  const sj::Layout lay(n_jobs, s->rows.n);
+  if (!lay.ok) return msha::bad_arg(s->ctx, kEntry, "the workspace size does not fit 64 bits");
+
+  return msha::guard(s->ctx, [&] {
+    // a capturing stream allows no allocation: know that before the workspace would grow
+    const bool capturing = stream && msha::stream_capturing(static_cast<hipStream_t>(stream));
+    DstreamJobs& js = s->jobs;
+    if (capturing && lay.bytes > js.ws_bytes)
+      throw msha::MshaError(MSHA_ERR_INVALID_ARG,
+                            std::string(kEntry) + ": the workspace cannot grow while the stream is being captured: "
+                                                  "make one call of this size outside the capture first");
+    msha::CtxDevice d;  // the set's own (s->dev): the context's first device
+    const hipStream_t st = msha::device_entry(s->ctx, kEntry, stream, capturing, &d);
+
+    if (lay.bytes > js.ws_bytes) {
+      // an earlier call may still be using the old buffer
+      if (js.last && js.ran) HIPCHK(hipEventSynchronize(js.last));
+      if (js.ws) HIPCHK(hipFree(js.ws));
+      js.ws = nullptr;
+      js.ws_bytes = 0;
+      js.ran = false;
+      const uint64_t want = lay.bytes + lay.bytes / 4;
+      HIPCHK(hipMalloc(&js.ws, want));
+      js.ws_bytes = want;
+    }
+    if (!js.last && !capturing) HIPCHK(hipEventCreateWithFlags(&js.last, hipEventDisableTiming));
+    // two streams must not race on the workspace: after the previous call's last kernel
+    if (!capturing && js.ran && js.last) HIPCHK(hipStreamWaitEvent(st, js.last, 0));
+
+    uint8_t* ws = static_cast<uint8_t*>(js.ws);
+    msha::StreamJobsArgs a;
+    a.job_stream = d_job_stream;
+    a.job_off = d_job_off;
+    a.job_len = d_job_len;
+    a.n_jobs = n_jobs;
+    a.n_streams = s->rows.n;
+    a.pairs[0] = reinterpret_cast<uint2*>(ws + lay.pairs[0]);
+    a.pairs[1] = reinterpret_cast<uint2*>(ws + lay.pairs[1]);
+    a.goff = reinterpret_cast<uint64_t*>(ws + lay.off);
+    a.glen = reinterpret_cast<uint64_t*>(ws + lay.len);
+    a.counts = reinterpret_cast<uint32_t*>(ws + lay.counts);
+    a.begin = reinterpret_cast<uint64_t*>(ws + lay.begin);
+    a.err = s->dev.err;
+    a.passes = sj::pass_count(s->rows.n);
+
+    msha::LaunchTimer timer(st, !capturing && msha::LaunchTimer::wanted());
+    uint32_t sort_launches = 0, row_launches = 0;
+    msha::launch_check(msha::launch_stream_jobs(a, st, &sort_launches, &row_launches), "stream jobs launch");
+    // Write's kernel over all n streams: a stream without a job stores nothing
+    msha::launch_check(msha::launch_dstream_write(s->rows, d_arena, a.goff, a.glen, a.begin, nullptr, s->rows.n,
+                                                  s->dev.err, st),
+                       "k_dstream_write launch");
+    js.ran = true;
+    js.last_jobs = n_jobs;
+    js.last_passes = a.passes;
+    if (!capturing) HIPCHK(hipEventRecord(js.last, st));
+    const float ms = timer.stop();
+    msha_dstreams_jobs_stats& t = js.st;
+    t.calls++;
+    t.jobs += n_jobs;
+    t.launches_sort += sort_launches;
+    t.launches_rows += row_launches;
+    t.launches_write++;
+    t.last_passes = a.passes;
+    t.last_jobs = n_jobs;
+    t.last_kernel_ms = ms;
+  });
+}
+
+int msha_dstreams_get_jobs_stats(const msha_dstreams* s, msha_dstreams_jobs_stats* out) {
+  if (!s || !out) return MSHA_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
+  *out = s->jobs.st;
+  return MSHA_OK;
+}
+
+int msha_dstreams_jobs_read_order(msha_dstreams* s, uint32_t* order, uint64_t cap, uint64_t* n_jobs,
+                                  uint64_t* n_valid) {
+  namespace sj = msha::sjobs;
+  if (!s || !n_jobs || !n_valid || (cap && !order)) return MSHA_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
+  *n_jobs = *n_valid = 0;
+  const DstreamJobs& js = s->jobs;
+  if (!js.ran) return MSHA_OK;
+  return msha::guard(s->ctx, [&] {
+    HIPCHK(hipSetDevice(s->dev.id));
+    HIPCHK(hipDeviceSynchronize());
+    const sj::Layout lay(js.last_jobs, s->rows.n);
+    const uint8_t* ws = static_cast<const uint8_t*>(js.ws);
+    uint64_t valid = 0;
+    HIPCHK(hipMemcpy(&valid, ws + lay.begin + 8 * s->rows.n, 8, hipMemcpyDeviceToHost));
+    *n_jobs = js.last_jobs;
+    *n_valid = valid < js.last_jobs ? valid : js.last_jobs;
+    const uint64_t k = js.last_jobs < cap ? js.last_jobs : cap;
+    if (k == 0) return;
+    std::vector<uint32_t> pairs(2 * k);  // (key, job index)
+    HIPCHK(hipMemcpy(pairs.data(), ws + lay.pairs[sj::sorted_buffer(js.last_passes)], 8 * k, hipMemcpyDeviceToHost));
+    for (uint64_t p = 0; p < k; ++p) order[p] = pairs[2 * p + 1];
   });
 }
 

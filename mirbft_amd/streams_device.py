@@ -7,7 +7,10 @@ GPU. ``write_device`` appends parts that already sit in device memory (at any by
 offset of an arena), ``sum_device`` / ``snap_device`` / ``reset_device`` are
 NodeState's Sum(nil), Snap and a fresh hash (pkg/testengine/recorder.go:288-359); each
 is one kernel launch on the caller's stream with no host wait, so a sequence of them
-captures into a HIP graph. The device calls take torch tensors (``torch`` supplies
+captures into a HIP graph. ``write_jobs_device`` is ``StreamSet.write``'s job list in
+device memory -- jobs in call order, a stream named any number of times -- grouped by
+stream on the GPU inside the call: several launches, still on the caller's stream and
+capturable once its workspace exists. The device calls take torch tensors (``torch`` supplies
 device memory and streams only); ``lengths``, ``export_state`` and ``import_state``
 are synchronous and use numpy, in the layout ``StreamSet`` exports.
 """
@@ -77,7 +80,8 @@ class DeviceStreamSet:
         part_off / part_len / row_part_begin, 4-byte for rows, bytes for arena / out."""
         import torch
         dev = self._device_index()
-        sizes = {"arena": 1, "out": 1, "part_off": 8, "part_len": 8, "row_part_begin": 8, "rows": 4}
+        sizes = {"arena": 1, "out": 1, "part_off": 8, "part_len": 8, "row_part_begin": 8, "rows": 4,
+                 "job_stream": 4, "job_off": 8, "job_len": 8}
         for name, t in tensors.items():
             if t is None:
                 continue
@@ -120,6 +124,44 @@ class DeviceStreamSet:
         self._check(self._lib.msha_dstreams_write_device(
             self._handle(), arena.data_ptr(), part_off.data_ptr(), part_len.data_ptr(), row_part_begin.data_ptr(),
             self._ptr(rows), n_rows, Engine._stream_ptr(stream)))
+
+    def write_jobs_device(self, arena, job_stream, job_off, job_len, stream=None) -> None:
+        """StreamSet.write's job list in device memory: for j in call order, stream
+        job_stream[j] appends arena[job_off[j] : job_off[j] + job_len[j]]. A stream may
+        be named any number of times; its chunks append in job order. The jobs are
+        grouped by stream on the GPU inside the call (several kernel launches, all on
+        ``stream``). A job whose stream is >= n is dropped and reported by
+        ``Engine.device_status()``. The arena rules are write_device's."""
+        self._check_tensors(arena=arena, job_stream=job_stream, job_off=job_off, job_len=job_len)
+        n_jobs = job_stream.numel()
+        if job_off.numel() != n_jobs or job_len.numel() != n_jobs:
+            raise ValueError(f"job_stream has {n_jobs} entries, job_off {job_off.numel()}, job_len {job_len.numel()}")
+        if arena.data_ptr() % L.MSHA_DEVICE_ALIGN:
+            raise ValueError(f"arena must start on a {L.MSHA_DEVICE_ALIGN}-byte boundary")
+        if n_jobs == 0:
+            return
+        if arena.numel() == 0:          # nothing to read: an empty tensor has no address to pass
+            arena = job_off.new_zeros(2)
+        self._check(self._lib.msha_dstreams_write_jobs_device(
+            self._handle(), arena.data_ptr(), job_stream.data_ptr(), job_off.data_ptr(), job_len.data_ptr(), n_jobs,
+            Engine._stream_ptr(stream)))
+
+    def jobs_stats(self) -> dict:
+        """The counters of write_jobs_device (stats() counts none of its calls)."""
+        s = L.MshaDstreamsJobsStats()
+        self._check(self._lib.msha_dstreams_get_jobs_stats(self._handle(), ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in L.MshaDstreamsJobsStats._fields_}
+
+    def jobs_order(self):
+        """(order, n_valid) of the last write_jobs_device (waits for the device): order[p]
+        is the job applied p-th -- argsort(min(job_stream, n), stable) -- and the first
+        n_valid of them name a stream of the set."""
+        k = self.jobs_stats()["last_jobs"]
+        order = np.zeros(max(k, 1), dtype=np.uint32)
+        n_jobs, n_valid = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.msha_dstreams_jobs_read_order(self._handle(), _p(order, ctypes.c_uint32), k,
+                                                            ctypes.byref(n_jobs), ctypes.byref(n_valid)))
+        return order[:n_jobs.value], n_valid.value
 
     def _finish(self, fn, out, rows, stream) -> None:
         self._check_tensors(out=out, rows=rows)

@@ -4,6 +4,7 @@ recorder's shape, and kernel against kernel over tools/parts_bench.py's part lis
 
     python3 tools/dstream_bench.py recorder [--reps 7] [--out profiles/streams_device/recorder.jsonl]
     python3 tools/dstream_bench.py kernel   [--reps 7] [--out profiles/streams_device/kernel.jsonl]
+    python3 tools/dstream_bench.py jobs     [--reps 7] [--out profiles/streams_device/jobs.jsonl]
 
 recorder  `--streams` (65,536) streams each appending `--digests` (20) 32-byte digests that
           sit in HBM as rows of a digest table (NodeState.Apply's shape, recorder.go:348).
@@ -19,6 +20,19 @@ kernel    k_dstream_write against k_digest_parts over the same part lists, lanes
           A write compresses the whole blocks only (no padding block), so each kernel's
           ns per lane-block is over the blocks it compressed; the ratio of the launch
           times is printed too.
+jobs      the recorder's shape as NodeState.Apply produces it: the `--streams` x `--digests`
+          digests arrive in commit order, job d * streams + s, the worst interleaving for a
+          grouping by stream. Three routes to the same streams, each a write + sum_device
+          with one synchronisation at the end, alternating after a warm repetition of each:
+          (a) write_device with the grouped CSR given (the floor: the caller already did
+              the grouping);
+          (b) what a Python caller can do without this entry: torch.sort(stable=True) on
+              the ids, searchsorted for the CSR, two gathers, then write_device;
+          (c) write_jobs_device.
+          (c) - (a) is the grouping's cost, (c) against (b) the gain over torch's sort.
+          The same again for one small call (64 streams x 20 digests): the launch-bound
+          end. Every stream's digest of every route is checked against hashlib outside
+          the timed window.
 Every figure is the median of `--reps` (>= 5) timed repetitions after warm ones, with
 (max - min) / median beside it. A sample of what was timed is checked against hashlib.
 A measurement, not a threshold. Needs the GPU; there is no fallback.
@@ -112,6 +126,78 @@ def recorder(a, build):
              "device_launches": st["launches"], "build": build["id"]}]
 
 
+def _jobs_shape(eng, n, k, reps, build, label):
+    import torch
+    from mirbft_amd import DeviceStreamSet
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(9)
+    table = torch.randint(0, 256, (n * k * 32 + 64,), dtype=torch.uint8, device=dev, generator=g)
+    # commit-major: job j = d * n + s is digest d of stream s, at table row j
+    job_stream = torch.arange(n, dtype=torch.int32, device=dev).repeat(k)
+    job_off = torch.arange(n * k, dtype=torch.int64, device=dev) * 32
+    job_len = torch.full((n * k,), 32, dtype=torch.int64, device=dev)
+    # (a)'s input, prepared outside the window: the same jobs grouped by stream
+    perm = torch.arange(n * k, dtype=torch.int64, device=dev).view(k, n).t().contiguous().view(-1)
+    g_off, g_len = job_off[perm].contiguous(), job_len[perm].contiguous()
+    begin = torch.arange(n + 1, dtype=torch.int64, device=dev) * k
+    out = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+    host = table.cpu().numpy()[: n * k * 32].reshape(k, n, 32)
+    want = np.frombuffer(b"".join(hashlib.sha256(host[:, s].tobytes()).digest() for s in range(n)),
+                         dtype=np.uint8).reshape(n, 32)
+    torch.cuda.synchronize()
+
+    def route_a(ds):
+        ds.write_device(table, g_off, g_len, begin)
+
+    def route_b(ds):
+        keys, order = torch.sort(job_stream, stable=True)
+        b = torch.searchsorted(keys, torch.arange(n + 1, dtype=torch.int32, device=dev)).to(torch.int64)
+        torch.cuda.current_stream().synchronize()      # torch's stream, then the context's: what a caller must do
+        ds.write_device(table, job_off[order].contiguous(), job_len[order].contiguous(), b)
+
+    def route_c(ds):
+        ds.write_jobs_device(table, job_stream, job_off, job_len)
+
+    times = {"a": [], "b": [], "c": []}
+    passes = launches = 0
+    with DeviceStreamSet(eng, n) as ds:
+        for rep in range(reps + 1):                    # the first of each is the warm one
+            for name, route in (("a", route_a), ("b", route_b), ("c", route_c)):
+                ds.reset_device()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                route(ds)
+                ds.sum_device(out)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                # every digest, outside the window
+                assert np.array_equal(out.cpu().numpy(), want), (label, name, rep)
+                if rep:
+                    times[name].append((t1 - t0) * 1e3)
+        eng.device_status()
+        js = ds.jobs_stats()
+        passes, launches = js["last_passes"], (js["launches_sort"] + js["launches_rows"] + js["launches_write"]) // js["calls"]
+    a_, b_, c_ = (_stat(times[x]) for x in "abc")
+    spread = lambda s: s["max"] - s["min"]             # noqa: E731
+    return {"measure": "jobs", "shape": label, "streams": n, "digests_per_stream": k, "jobs": n * k, "reps": reps,
+            "csr_given_ms": a_, "torch_sort_ms": b_, "write_jobs_ms": c_,
+            "grouping_cost_ms": round(c_["median"] - a_["median"], 4),
+            "jobs_minus_torch_ms": round(c_["median"] - b_["median"], 4),
+            "jobs_over_torch": round(c_["median"] / b_["median"], 3),
+            "spreads_jobs_torch_ms": round(spread(b_) + spread(c_), 4),
+            "jobs_slower_than_torch_by_more_than_the_spreads": bool(c_["median"] - b_["median"] > spread(b_) + spread(c_)),
+            "jobs_faster_than_torch_by_more_than_the_spreads": bool(b_["median"] - c_["median"] > spread(b_) + spread(c_)),
+            "passes": passes, "launches_per_jobs_call": launches, "build": build["id"]}
+
+
+def jobs(a, build):
+    from mirbft_amd import Engine
+    with Engine(1) as eng:
+        return [_jobs_shape(eng, a.streams, a.digests, a.reps, build, "recorder"),
+                _jobs_shape(eng, 64, 20, a.reps, build, "small")]
+
+
 def _blocks(length):
     length = length.astype(np.uint64)
     return (length >> np.uint64(6)) + np.where((length & np.uint64(63)) < 56, 1, 2).astype(np.uint64)
@@ -195,7 +281,7 @@ def kernel(a, build):
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("measure", choices=["recorder", "kernel"])
+    ap.add_argument("measure", choices=["recorder", "kernel", "jobs"])
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--streams", type=int, default=1 << 16)
     ap.add_argument("--digests", type=int, default=20)
@@ -210,10 +296,10 @@ def main() -> int:
     if a.measure == "kernel":
         os.environ["MSHA_PARTS_TIMING"] = "1"      # read by the library at each call
     elif os.environ.get("MSHA_PARTS_TIMING") == "1":
-        ap.error("recorder measures enqueue-only calls: unset MSHA_PARTS_TIMING")
+        ap.error("%s measures enqueue-only calls: unset MSHA_PARTS_TIMING" % a.measure)
     from mirbft_amd import _lib
     build = _lib.require_tree_build("dstream_bench")
-    lines = recorder(a, build) if a.measure == "recorder" else kernel(a, build)
+    lines = {"recorder": recorder, "kernel": kernel, "jobs": jobs}[a.measure](a, build)
     for ln in lines:
         print(json.dumps(ln))
     if a.out:
