@@ -382,6 +382,27 @@ int msha_absorb_device(msha_ctx* ctx, uint32_t* d_state, const uint8_t* d_arena,
 int msha_finish_device(msha_ctx* ctx, const uint32_t* d_state, const uint64_t* d_prefix,
                        const uint8_t* d_arena, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
                        uint8_t* d_out, void* stream);
+/*
+ * Absorb on the eight-lane chain (ABI 10, additive: MSHA_HAS_ABSORB_CHAIN tells a build
+ * that has it). The contract is msha_absorb_device's, word for word: the same arguments,
+ * device memory of the context's first device, starts MSHA_DEVICE_ALIGN-aligned,
+ * MSHA_DEVICE_ARENA_SLACK readable bytes after the last lane's bytes, errors through
+ * msha_device_status, the same host checks, n == 0 launches nothing; a lane with no
+ * block, or with a misaligned start (reported once), leaves its state as it was; and the
+ * states afterwards are bit for bit msha_absorb_device's. What differs is the kernel:
+ * msha_absorb_device gives a lane one GPU lane, so a lone long lane runs at one lane's
+ * rate; here a lane is eight GPU lanes and a share of two producer waves, the round
+ * engine of the eight-lane digest chain resumed from the given state and stopped
+ * without padding. It is for FEW, LONG lanes: 16 lanes a workgroup, one workgroup a
+ * compute unit, so beyond 16 x compute units lanes the workgroups queue
+ * (profiles/streams_device/README.md says where it stops paying). One launch on
+ * `stream` (NULL: the context's own), no host wait: capturable. No block is read past a
+ * lane's last. msha_set_kernel_policy does not apply. The launch counts in msha_stats
+ * as every chain launch does: launches_coop and launches_chain8.
+ */
+#define MSHA_HAS_ABSORB_CHAIN 1
+int msha_absorb_chain_device(msha_ctx* ctx, uint32_t* d_state, const uint8_t* d_arena,
+                             const uint64_t* d_off, const uint64_t* d_nblocks, uint64_t n, void* stream);
 
 /*
  * Device stream sets: the stream sets above with everything in device memory (ABI 10,
@@ -860,6 +881,92 @@ int msha_parts_route_read(msha_ctx* ctx, uint32_t* lists, uint64_t cap, uint64_t
 /* The same for the lanes that remained: the last routed call's lane order, as
  * msha_parts_plan_read_order gives the planned entry's. */
 int msha_parts_route_read_order(msha_ctx* ctx, uint32_t* order, uint64_t cap, uint64_t* lanes);
+
+/*
+ * Device stream sets: long writes routed to the chain (ABI 10, additive:
+ * MSHA_HAS_STREAMS_DEVICE_ROUTED tells a build that has it). In a device stream set one
+ * stream is one lane, which is right for tens of thousands of streams taking a few
+ * digests each. NodeState.ActiveHash (pkg/testengine/recorder.go:288-359) is the other
+ * shape: one stream a node, a handful of streams, each taking every committed request
+ * digest between two checkpoints -- thousands of blocks in a row on a handful of lanes.
+ * This entry is msha_dstreams_write_device with the decision made on the GPU inside the
+ * call: it finds the rows whose write compresses many blocks, flattens each behind its
+ * stream's buffered bytes and runs them on the eight-lane chain (the kernel of
+ * msha_absorb_chain_device), and writes the other rows as lanes.
+ *
+ * SAME RESULT, SAME ERRORS as msha_dstreams_write_device. Rows and the row contract (a
+ * stream at most once a call; a repeat leaves that stream alone unspecified and touches
+ * nothing outside the set), the READ CONTRACT, the host checks (null pointers,
+ * d_arena's alignment, n_rows >= 2^32 - 1, d_row NULL with n_rows != n), bit 32 for a
+ * row naming a stream >= n and bit 4 for a decreasing part range (either stream
+ * untouched), empty parts and zero-part rows contributing nothing, n_rows == 0
+ * launching nothing: all are that entry's. Also checked on the host: the bounds of
+ * `opts` (msha_route_opts above, the same bounds). Routing is an optimisation: no input
+ * makes a stream's state, buffer or length differ from that entry's, and nothing here
+ * raises bit 16.
+ *
+ * WHAT IS ROUTED. A row is LONG when its stream is < n, its part range is valid and
+ *   whole = floor((length[s] % 64 + the sum of its part lengths) / 64) >= long_blocks,
+ * whole being the blocks the write compresses. A long row claims a slot, then room for
+ * round16(length[s] % 64 + sum) bytes, by the rules of msha_hash_actions_device_routed
+ * (CAPS NEVER FAIL A CALL, above): a row that gets no slot or no room stays a lane and
+ * is as right as any; when every long row fits both caps exactly the long rows are
+ * routed; of long rows of one total L = length[s] % 64 + sum exactly
+ * min(n_long, max_long, floor((long_bytes - MSHA_DEVICE_ARENA_SLACK) / round16(L))) are.
+ *
+ * DEFAULTS (a zero field, or opts NULL): max_long 16 x compute units, long_bytes 32 MiB,
+ * long_blocks MSHA_DSTREAMS_ROUTE_LONG_BLOCKS_DEFAULT = 64, the routed parts entry's
+ * threshold. tools/dstream_bench.py's `long` measure sweeps it from 8 to 256
+ * (profiles/streams_device/long.jsonl and README.md): where the long rows are far above
+ * it the medians differ by less than their spreads, so 64 stays; a threshold so low that
+ * most of many thousand short rows count as long is the one setting measured to lose,
+ * by a wide margin. With no long row the call costs three launches that find nothing to
+ * do and two more than write_device; the same files name that loss.
+ *
+ * SIX LAUNCHES, all on `stream` (NULL: the context's own), whatever the rows hold: init,
+ * measure, copy, chain, tail, write. No memset, no library stream, no host wait; the
+ * call captures into a HIP graph as a chain of kernel nodes (a replay appends again).
+ * With no long row the copy, the chain and the tail find nothing to do. No kernel waits
+ * on another workgroup.
+ *
+ * The workspace (a byte a row, 36 bytes a slot and the flatten buffer of long_bytes)
+ * belongs to the set and is freed in destroy. Growth, the refusal on a capturing stream
+ * and the event that orders a call after the set's previous routed call are those of
+ * msha_dstreams_write_jobs_device; the two entries share no memory.
+ *
+ * MSHA_PARTS_TIMING and MSHA_PARTS_PLAN_WAVE_SUM apply as in the routed parts entry.
+ */
+#define MSHA_HAS_STREAMS_DEVICE_ROUTED 1
+#define MSHA_DSTREAMS_ROUTE_LONG_BLOCKS_DEFAULT 64u
+int msha_dstreams_write_routed_device(msha_dstreams* set, const uint8_t* d_arena,
+                                      const uint64_t* d_part_off, const uint64_t* d_part_len,
+                                      const uint64_t* d_row_part_begin, const uint32_t* d_row,
+                                      uint64_t n_rows, const msha_route_opts* opts, void* stream);
+/* Counters of msha_dstreams_write_routed_device (msha_dstreams_stats and
+ * msha_dstreams_jobs_stats count none of its calls; its chain launch counts in msha_stats
+ * as every chain launch does: launches_coop and launches_chain8). */
+typedef struct {
+  uint64_t calls;             /* calls that enqueued their launches */
+  uint64_t rows;              /* rows of those calls */
+  uint64_t launches_route;    /* init and measure: 2 a call */
+  uint64_t launches_copy;     /* the flatten: one a call */
+  uint64_t launches_chain;    /* the eight-lane absorb chain: one a call */
+  uint64_t launches_tail;     /* the routed streams' tail rows and lengths: one a call */
+  uint64_t launches_write;    /* Write's row body over the rows that stayed lanes: one a call */
+  uint64_t last_routed;       /* the last call's routed rows and ... */
+  uint64_t last_routed_bytes; /* ... the bytes of the flatten buffer they were given; both read back, and */
+  double last_kernel_ms;      /* the call's kernels timed by HIP events, only under MSHA_PARTS_TIMING=1
+                                 (read at each call; the call then waits for its kernels; never while
+                                 `stream` is being captured); otherwise these three are 0 */
+} msha_dstreams_route_stats;
+int msha_dstreams_get_route_stats(const msha_dstreams* set, msha_dstreams_route_stats* out);
+/* Diagnostic, synchronous, like msha_parts_route_read: waits for the device, then copies
+ * the row indices (r, not the streams) the set's last routed call routed, in no
+ * particular order, into rows[0 .. min(cap, *n_routed)), their count into *n_routed and
+ * the bytes of the flatten buffer they were given into *routed_bytes. rows may be NULL
+ * when cap is 0. Before any routed call both counts are 0. */
+int msha_dstreams_route_read(msha_dstreams* set, uint32_t* rows, uint64_t cap, uint64_t* n_routed,
+                             uint64_t* routed_bytes);
 
 /*
  * Host-only helpers (no GPU needed).

@@ -39,6 +39,9 @@ MSHA_ROUTE_LONG_BLOCKS_DEFAULT = 64
 MSHA_ROUTE_LONG_BYTES_DEFAULT = 32 << 20
 MSHA_HAS_STREAMS_DEVICE = 1
 MSHA_HAS_STREAMS_DEVICE_JOBS = 1
+MSHA_HAS_ABSORB_CHAIN = 1
+MSHA_HAS_STREAMS_DEVICE_ROUTED = 1
+MSHA_DSTREAMS_ROUTE_LONG_BLOCKS_DEFAULT = 64
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -211,6 +214,21 @@ class MshaDstreamsJobsStats(ctypes.Structure):
     ]
 
 
+class MshaDstreamsRouteStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", ctypes.c_uint64),
+        ("rows", ctypes.c_uint64),
+        ("launches_route", ctypes.c_uint64),
+        ("launches_copy", ctypes.c_uint64),
+        ("launches_chain", ctypes.c_uint64),
+        ("launches_tail", ctypes.c_uint64),
+        ("launches_write", ctypes.c_uint64),
+        ("last_routed", ctypes.c_uint64),
+        ("last_routed_bytes", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
 _setp = ctypes.c_void_p
 
 # name -> (restype, argtypes)
@@ -264,6 +282,8 @@ SIGNATURES = {
     "msha_streams_get_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaStreamsStats)]),
     "msha_absorb_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "msha_absorb_chain_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "msha_finish_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                           ctypes.c_void_p]),
@@ -307,6 +327,11 @@ SIGNATURES = {
                                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "msha_dstreams_get_jobs_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaDstreamsJobsStats)]),
     "msha_dstreams_jobs_read_order": (ctypes.c_int, [_setp, _u32p, ctypes.c_uint64, _u64p, _u64p]),
+    "msha_dstreams_write_routed_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                         ctypes.POINTER(MshaRouteOpts), ctypes.c_void_p]),
+    "msha_dstreams_get_route_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaDstreamsRouteStats)]),
+    "msha_dstreams_route_read": (ctypes.c_int, [_setp, _u32p, ctypes.c_uint64, _u64p, _u64p]),
 }
 
 _lib = None
@@ -357,6 +382,7 @@ _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mi
               "parts_digest.hpp", "parts_plan.hpp", "parts_plan.hip", "parts_plan.cpp",
               "parts_route.hpp", "parts_route.cpp",
               "stream_device.hpp", "stream_device.hip", "stream_device.cpp", "stream_jobs.hpp", "stream_jobs.hip",
+              "stream_chain.hpp", "stream_chain.hip", "stream_write.hpp",
               "parts_concat.hpp", "parts_concat.hip", "parts_concat.cpp")
 
 

@@ -23,6 +23,7 @@
 
 #include "sha256_device.hpp"
 #include "kernels.hpp"
+#include "stream_chain.hpp"
 
 namespace msha {
 
@@ -1623,6 +1624,160 @@ __global__ __launch_bounds__(256) void k_digest_chain8(const uint8_t* __restrict
   MSHA_WAVE_STAMP_CLOSE(kStampChain8)
 }
 
+// ---------------------------------------------------------------------------
+// The eight-lane chain resumed from a state (msha_absorb_chain_device; the chain
+// of msha_dstreams_write_routed_device): chain8_body's round engine -- the same
+// rounds, K+W form, two producers, two consumer waves, 16 lanes a workgroup and
+// pair path -- over whole blocks only. A lane's consumers start from its state
+// row (a-quad: words 0-3, e-quad: words 4-7, host order) instead of the initial
+// value, its producers schedule nblocks whole blocks (no padded tail, no length
+// block, and no prefetch past the lane's last block), and the lane whose last
+// block it was stores the row back as it is, with no byte swap. A lane of no
+// blocks, an unfilled slot (row[i] == kNoLane) or a misaligned start (bit 0 of
+// *err, raised once) stores nothing. Lane i works on state row row ? row[i] : i.
+// Which producer takes which block, the slot it fills and where the barriers
+// fall: stream_chain.hpp, whose two barrier counts the host compares. A
+// workgroup takes the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of 16 lanes;
+// every wave of it makes the same barrier calls for a tile, so a tile whose NB
+// is 0 is left by all four right after NB is known.
+// ---------------------------------------------------------------------------
+static_assert(schain::kProducers == kC8Producers && schain::kPairMinBlocks == kC2PairMinBlocks,
+              "stream_chain.hpp states this kernel's schedule");
+#define MSHA_ABLOCK8(cur, nxt)                                                                   \
+  {                                                                                              \
+    uint32_t X = H0, Y = H1, Z = H2, W = H3;                                                     \
+    _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) MSHA_DQ8(cur, nxt, q_)                      \
+    H0 += X; H1 += Y; H2 += Z; H3 += W;                                                          \
+    if (sub == 0 && b + 1 == nb) *reinterpret_cast<uint4*>(srow) = make_uint4(H0, H1, H2, H3);   \
+  }
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_absorb_chain8(uint32_t* state, const uint8_t* __restrict__ arena,
+                                                       const uint64_t* __restrict__ off,
+                                                       const uint64_t* __restrict__ nblocks,
+                                                       const uint32_t* __restrict__ row, uint64_t n,
+                                                       uint32_t* __restrict__ err) {
+  static_assert(MSHA_CHAIN2_FORM == 4, "the eight-lane rounds read form 4's K+W layout");
+  __shared__ uint4 kw[2][kC2Per][kCoopSlotQuads * 64];
+  __shared__ uint32_t s_nb;
+  const unsigned lane = threadIdx.x & 63;
+  const unsigned wave = threadIdx.x >> 6;
+  const bool producer = wave < kC8Producers;
+  const bool eside = (lane & 4) == 0;
+  const unsigned sub = lane & 3;
+  const unsigned msg = producer ? lane : (wave - kC8Producers) * 8 + (lane >> 3);
+  const uint32_t sh = eside ? (sub == 1 ? 11u : sub == 2 ? 25u : 6u) : (sub == 1 ? 13u : sub == 2 ? 22u : 2u);
+  const unsigned col = (eside ? 0 : 64) + msg;  // form 4: even rounds' quads, then the odd rounds'
+  const uint64_t tiles = (n + kChain8MsgsPerWg - 1) / kChain8MsgsPerWg;
+  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const uint64_t i = tile * kChain8MsgsPerWg + msg;
+    bool active = msg < kChain8MsgsPerWg && i < n;
+    uint64_t r = i;  // state row
+    if (active && row) {
+      const uint32_t v = row[i];
+      active = v != kNoLane;
+      r = v;
+    }
+    const uint8_t* pa = arena;
+    uint32_t nb = 0;  // this lane's blocks; 0: nothing is loaded, nothing is stored
+    if (active) {
+      const uint64_t k = nblocks[i];
+      nb = k < 0xFFFFFFFEull ? (uint32_t)k : 0xFFFFFFFEu;
+      pa = arena + off[i];
+      if (nb != 0 && (reinterpret_cast<uintptr_t>(pa) & 15)) {  // flagged; the state stays as it was
+        nb = 0;
+        if (!producer && eside && sub == 0) atomicOr(err, 1u);
+      }
+    }
+    if (nb == 0) r = 0;
+    uint32_t* const srow = state + 8 * r + (eside ? 4 : 0);
+    if (threadIdx.x == 0) s_nb = 0;
+    __syncthreads();
+    if (producer && nb != 0) atomicMax(&s_nb, nb);
+    __syncthreads();
+    const uint32_t NB = s_nb;  // the same for every wave of the workgroup
+    if (NB == 0) continue;
+    const uint32_t per = schain::per_for(NB, kC2Per);
+    if (producer) {
+      const uint32_t pw = wave;
+      uint32_t raw[16], w[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) raw[j] = w[j] = 0;
+      if (schain::prefetch_ok(pw, nb)) load_block16<MODE>(pa + 64 * (uint64_t)pw, raw);
+      for (uint32_t b = 0; b < NB; ++b) {
+        if (schain::producer_of(b) == pw) {
+          // past the lane's last block the slot gets the words at hand: the consumers
+          // run on, and what they compute there is never stored
+          if (b < nb) to_words(raw, w);
+          if (schain::prefetch_ok(b + kC8Producers, nb))
+            load_block16<MODE>(pa + 64 * (uint64_t)(b + kC8Producers), raw);
+          schedule_kw_eo(w, &kw[schain::slot_of(b, per)][schain::sub_of(b, per)][lane]);
+        }
+        if (schain::producer_barrier_after(b, NB, per)) MSHA_C2_BARRIER(b / per)  // barrier g: slot g & 1 holds group g
+      }
+      MSHA_C2_BARRIER(schain::groups(NB, per))  // the consumers' last (they wait one group ahead)
+    } else {
+      uint32_t H0 = 0, H1 = 0, H2 = 0, H3 = 0;
+      if (nb != 0) {
+        const uint4 v = *reinterpret_cast<const uint4*>(srow);
+        H0 = v.x; H1 = v.y; H2 = v.z; H3 = v.w;
+      }
+#if MSHA_CHAIN2_PAIR
+      if (per == 2) {
+        uint4 ka[8], kb[8], kc[8], kd[8];
+        MSHA_C2_BARRIER(0)  // barrier 0: slot 0 holds blocks 0 and 1
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          ka[q] = kw[0][0][col + q * 128];
+          kb[q] = kw[0][1][col + q * 128];
+        }
+        const uint32_t NP = schain::groups(NB, 2);
+        for (uint32_t g = 0; g < NP; ++g) {
+          MSHA_C2_BARRIER(g + 1)  // reads past the last block are harmless (unused)
+          {
+            const uint32_t b = 2 * g;
+            const uint4* nk = kw[(g + 1) & 1][0];
+            MSHA_ABLOCK8(ka, kc)
+          }
+          {
+            const uint32_t b = 2 * g + 1;
+            const uint4* nk = kw[(g + 1) & 1][1];
+            MSHA_ABLOCK8(kb, kd)
+          }
+          if (++g == NP) break;
+          MSHA_C2_BARRIER(g + 1)
+          {
+            const uint32_t b = 2 * g;
+            const uint4* nk = kw[(g + 1) & 1][0];
+            MSHA_ABLOCK8(kc, ka)
+          }
+          {
+            const uint32_t b = 2 * g + 1;
+            const uint4* nk = kw[(g + 1) & 1][1];
+            MSHA_ABLOCK8(kd, kb)
+          }
+        }
+        continue;
+      }
+#endif
+      uint4 ka[8], kb[8];
+      MSHA_C2_BARRIER(0)  // barrier 0: slot 0 holds block 0
+#pragma unroll
+      for (int q = 0; q < 8; ++q) ka[q] = kw[0][0][col + q * 128];
+      for (uint32_t b = 0; b < NB; ++b) {
+        MSHA_C2_BARRIER(b + 1)
+        const uint4* nk = kw[(b + 1) & 1][0];  // a read past the last block is harmless (unused)
+        MSHA_ABLOCK8(ka, kb)
+        if (++b == NB) break;
+        MSHA_C2_BARRIER(b + 1)
+        nk = kw[(b + 1) & 1][0];
+        MSHA_ABLOCK8(kb, ka)
+      }
+    }
+  }
+}
+#undef MSHA_ABLOCK8
+
 #undef MSHA_DBLOCK8
 #undef MSHA_DQ8
 #undef MSHA_ASM8_OPERANDS
@@ -1925,6 +2080,18 @@ hipError_t launch_digest_of_digests(const uint8_t* table, const uint32_t* idx,
   hipLaunchKernelGGL(k_digest_of_digests, dim3(grid_for(n)), dim3(256), 0, st, table, idx, begin,
                      n, out);
   set_kind(kind, kLaunchDod);
+  return hipGetLastError();
+}
+
+hipError_t launch_absorb_chain8(uint32_t* state, const uint8_t* arena, const uint64_t* off, const uint64_t* nblocks,
+                                const uint32_t* row, uint64_t n, uint32_t* err, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  // a workgroup per 16 lanes, one workgroup a CU as AUTO's small launches of
+  // k_digest_chain8 (64 KiB of dynamic LDS on top of its 64 KiB); grid x block stays
+  // below 2^32: past 2^22 workgroups one takes several tiles
+  const uint64_t tiles = (n + kChain8MsgsPerWg - 1) / kChain8MsgsPerWg, cap = 1ull << 22;
+  hipLaunchKernelGGL(k_absorb_chain8<kPrefetch>, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(256), 64 * 1024,
+                     st, state, arena, off, nblocks, row, n, err);
   return hipGetLastError();
 }
 

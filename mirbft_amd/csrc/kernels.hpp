@@ -292,6 +292,13 @@ hipError_t launch_stream_rows_set(uint32_t* state, const uint32_t* row, const ui
 hipError_t launch_stream_rows_get(const uint32_t* state, const uint32_t* row, uint32_t* out, uint64_t n,
                                   hipStream_t st);
 
+// absorb on the eight-lane chain (kernels.hip k_absorb_chain8, msha_absorb_chain_device):
+// launch_stream_absorb's lanes, rules and result with eight lanes and a producer's share
+// a lane, 16 lanes a workgroup, one workgroup a CU. row[i] == kNoLane: lane i is idle.
+// One launch, any n < 2^32.
+hipError_t launch_absorb_chain8(uint32_t* state, const uint8_t* arena, const uint64_t* off, const uint64_t* nblocks,
+                                const uint32_t* row, uint64_t n, uint32_t* err, hipStream_t st);
+
 // Device stream sets (stream_device.hip, msha_dstreams_*): a stream is row s of three
 // device arrays -- state + 8 s (eight host-order words), tail + 64 s (the buffered
 // length % 64 bytes, zero past them) and length + s. Lane i works on stream
@@ -348,6 +355,45 @@ struct StreamJobsArgs {
 };
 hipError_t launch_stream_jobs(const StreamJobsArgs& a, hipStream_t st, uint32_t* sort_launches,
                               uint32_t* row_launches);
+
+// Write with its long rows routed to the eight-lane chain (stream_chain.hip,
+// msha_dstreams_write_routed_device). A routed row holds a slot k < max_long:
+// slot_row[k] its row, slot_stream[k] its stream (schain::kNoStream when nobody filled
+// the slot), slot_t[k] the bytes the stream buffered, msg_len[k] = slot_t[k] + the sum of
+// its part lengths, its message at flat + msg_off[k], blocks[k] the whole blocks the
+// chain compresses; taken[r] = 1 marks row r as the chain's. Decisions and layout:
+// stream_chain.hpp; claim rules: parts_route.hpp.
+struct StreamRouteArgs {
+  DstreamRows rows;
+  const uint8_t* arena = nullptr;
+  const uint64_t* part_off = nullptr;
+  const uint64_t* part_len = nullptr;
+  const uint64_t* begin = nullptr;  // n_rows + 1
+  const uint32_t* row = nullptr;    // n_rows, or null
+  uint64_t n_rows = 0;
+  uint32_t long_blocks = 0;  // >= 1
+  uint32_t max_long = 0;     // slots
+  uint64_t long_bytes = 0;   // bytes of the flatten buffer
+  uint8_t* taken = nullptr;           // n_rows, rounded up to words
+  uint32_t* slot_row = nullptr;       // max_long each:
+  uint32_t* slot_stream = nullptr;
+  uint32_t* slot_t = nullptr;
+  uint64_t* msg_off = nullptr;
+  uint64_t* msg_len = nullptr;
+  uint64_t* blocks = nullptr;
+  unsigned long long* claim = nullptr;  // parts_route::kClaimWords counters
+  uint8_t* flat = nullptr;
+  uint32_t* err = nullptr;
+  uint32_t wave_sum_parts = 0;  // rows of this many parts or more are summed by their wave
+};
+// One launch each, in the order of the call: init, measure; copy; (the chain:
+// launch_absorb_chain8 over the slots); tail; write (Write's row body over the rows with
+// taken == 0).
+hipError_t launch_sroute_init(const StreamRouteArgs& a, hipStream_t st);
+hipError_t launch_sroute_measure(const StreamRouteArgs& a, hipStream_t st);
+hipError_t launch_sroute_copy(const StreamRouteArgs& a, hipStream_t st);
+hipError_t launch_sroute_tail(const StreamRouteArgs& a, hipStream_t st);
+hipError_t launch_dstream_write_rest(const StreamRouteArgs& a, hipStream_t st);
 
 // Multi-part actions (parts_kernels.hip k_digest_parts, msha_hash_actions_device): lane
 // i hashes action a = order ? order[i] : i, the concatenation of the parts

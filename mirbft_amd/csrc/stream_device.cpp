@@ -7,11 +7,15 @@
 // Length, export and import are synchronous and move whole streams through a staging
 // buffer of their own.
 //
-// msha_dstreams_write_jobs_device is the one device call of several launches: the jobs
-// are grouped by stream on the GPU (stream_jobs.hip) in a workspace the set owns, then
-// Write's kernel runs over all n streams. The workspace follows the rule of
+// Two device calls are several launches each, with a workspace the set owns.
+// msha_dstreams_write_jobs_device: the jobs are grouped by stream on the GPU
+// (stream_jobs.hip), then Write's kernel runs over all n streams.
+// msha_dstreams_write_routed_device: the rows whose write compresses many blocks are
+// found on the GPU, flattened behind their stream's buffered bytes and absorbed by the
+// eight-lane chain, the others written as lanes (stream_chain.hip, kernels.hip
+// k_absorb_chain8; six launches). Each workspace follows the rule of
 // msha_hash_actions_device_planned (parts_plan.cpp): it grows only outside stream
-// capture, and a call outside capture is ordered after the set's previous jobs call.
+// capture, and a call outside capture is ordered after the set's previous call of its kind.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -21,7 +25,9 @@
 
 #include "../../include/mirsha.h"
 #include "host_call.hpp"
+#include "stream_chain.hpp"
 #include "stream_device.hpp"
+#include "parts_plan.hpp"
 #include "stream_jobs.hpp"
 #include "stream_state.hpp"
 
@@ -37,12 +43,25 @@ struct DstreamJobs {
   msha_dstreams_jobs_stats st{};
 };
 
+// The workspace of the routed writes (stream_chain.hpp Layout) and what
+// msha_dstreams_route_read needs of the last one.
+struct DstreamRoute {
+  void* ws = nullptr;
+  uint64_t ws_bytes = 0;
+  hipEvent_t last = nullptr;  // recorded after the last call made outside capture
+  bool ran = false;
+  uint64_t last_slots = 0;
+  uint64_t at_row = 0, at_stream = 0, at_claim = 0;  // byte offsets in ws of the last call's arrays
+  msha_dstreams_route_stats st{};
+};
+
 struct msha_dstreams {
   msha_ctx* ctx = nullptr;
   msha::CtxDevice dev;
   msha::DstreamRows rows;
   msha_dstreams_stats st{};
   DstreamJobs jobs;
+  DstreamRoute route;
 };
 
 namespace {
@@ -68,6 +87,8 @@ void release(msha_dstreams* s) {
   if (s->rows.length) (void)hipFree(s->rows.length);
   if (s->jobs.ws) (void)hipFree(s->jobs.ws);  // waits for the device
   if (s->jobs.last) (void)hipEventDestroy(s->jobs.last);
+  if (s->route.ws) (void)hipFree(s->route.ws);  // waits for the device
+  if (s->route.last) (void)hipEventDestroy(s->route.last);
 }
 
 // The row arguments every device call shares. Call with the lock held.
@@ -298,6 +319,160 @@ int msha_dstreams_jobs_read_order(msha_dstreams* s, uint32_t* order, uint64_t ca
     std::vector<uint32_t> pairs(2 * k);  // (key, job index)
     HIPCHK(hipMemcpy(pairs.data(), ws + lay.pairs[sj::sorted_buffer(js.last_passes)], 8 * k, hipMemcpyDeviceToHost));
     for (uint64_t p = 0; p < k; ++p) order[p] = pairs[2 * p + 1];
+  });
+}
+
+int msha_dstreams_write_routed_device(msha_dstreams* s, const uint8_t* d_arena, const uint64_t* d_part_off,
+                                      const uint64_t* d_part_len, const uint64_t* d_row_part_begin,
+                                      const uint32_t* d_row, uint64_t n_rows, const msha_route_opts* opts,
+                                      void* stream) {
+  static const char* const kEntry = "msha_dstreams_write_routed_device";
+  namespace sc = msha::schain;
+  if (!s) return MSHA_ERR_INVALID_ARG;
+  if (n_rows == 0) return MSHA_OK;
+  std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
+  if (!d_arena || !d_part_off || !d_part_len || !d_row_part_begin)
+    return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
+  if (reinterpret_cast<uintptr_t>(d_arena) % MSHA_DEVICE_ALIGN)
+    return msha::bad_arg(s->ctx, kEntry, "d_arena must be 16-byte aligned");
+  const int rc = check_rows(s, kEntry, d_row, n_rows);
+  if (rc != MSHA_OK) return rc;
+  const msha_route_opts o = opts ? *opts : msha_route_opts{0, 0, 0};
+  if (o.long_bytes != 0 && o.long_bytes < 16 + MSHA_DEVICE_ARENA_SLACK)
+    return msha::bad_arg(s->ctx, kEntry, "opts->long_bytes (" + std::to_string(o.long_bytes) +
+                                             ") holds no row: it must be 0 or at least " +
+                                             std::to_string(16 + MSHA_DEVICE_ARENA_SLACK));
+  if (o.long_bytes > (1ull << 48))
+    return msha::bad_arg(s->ctx, kEntry, "opts->long_bytes (" + std::to_string(o.long_bytes) + ") is above 2^48");
+
+  return msha::guard(s->ctx, [&] {
+    // a capturing stream allows no allocation: know that before the workspace would grow
+    const bool capturing = stream && msha::stream_capturing(static_cast<hipStream_t>(stream));
+    msha::CtxDevice d;  // the set's own (s->dev): the context's first device
+    const hipStream_t st = msha::device_entry(s->ctx, kEntry, stream, capturing, &d);
+
+    // the slots are lanes of the eight-lane chain, one workgroup a CU
+    const uint64_t most = (uint64_t)d.cus * msha::kChain8MsgsPerWg;
+    if (o.max_long > most)
+      throw msha::MshaError(MSHA_ERR_INVALID_ARG, std::string(kEntry) + ": opts->max_long (" +
+                                                      std::to_string(o.max_long) + ") is above 16 x compute units (" +
+                                                      std::to_string(most) + ")");
+    msha::StreamRouteArgs a;
+    a.long_blocks = o.long_blocks ? o.long_blocks : MSHA_DSTREAMS_ROUTE_LONG_BLOCKS_DEFAULT;
+    a.max_long = o.max_long ? o.max_long : (uint32_t)most;
+    a.long_bytes = o.long_bytes ? o.long_bytes : MSHA_ROUTE_LONG_BYTES_DEFAULT;
+
+    DstreamRoute& rs = s->route;
+    const sc::Layout lay(n_rows, a.max_long, a.long_bytes);
+    if (!lay.ok) throw msha::MshaError(MSHA_ERR_INVALID_ARG, std::string(kEntry) + ": the workspace size does not fit");
+    if (capturing && lay.bytes > rs.ws_bytes)
+      throw msha::MshaError(MSHA_ERR_INVALID_ARG,
+                            std::string(kEntry) + ": the workspace cannot grow while the stream is being captured: "
+                                                  "make one call of this size outside the capture first");
+    if (lay.bytes > rs.ws_bytes) {
+      // an earlier call may still be using the old buffer
+      if (rs.last && rs.ran) HIPCHK(hipEventSynchronize(rs.last));
+      if (rs.ws) HIPCHK(hipFree(rs.ws));
+      rs.ws = nullptr;
+      rs.ws_bytes = 0;
+      rs.ran = false;
+      // the arrays grow with a quarter to spare, the flatten buffer is what was asked for
+      const uint64_t want = lay.bytes + lay.flat / 4;
+      HIPCHK(hipMalloc(&rs.ws, want));
+      rs.ws_bytes = want;
+    }
+    if (!rs.last && !capturing) HIPCHK(hipEventCreateWithFlags(&rs.last, hipEventDisableTiming));
+    // two streams must not race on the workspace: after the previous call's last kernel
+    if (!capturing && rs.ran && rs.last) HIPCHK(hipStreamWaitEvent(st, rs.last, 0));
+
+    uint8_t* ws = static_cast<uint8_t*>(rs.ws);
+    a.rows = s->rows;
+    a.arena = d_arena;
+    a.part_off = d_part_off;
+    a.part_len = d_part_len;
+    a.begin = d_row_part_begin;
+    a.row = d_row;
+    a.n_rows = n_rows;
+    a.claim = reinterpret_cast<unsigned long long*>(ws + lay.claim);
+    a.taken = ws + lay.taken;
+    a.slot_row = reinterpret_cast<uint32_t*>(ws + lay.slot_row);
+    a.slot_stream = reinterpret_cast<uint32_t*>(ws + lay.slot_stream);
+    a.slot_t = reinterpret_cast<uint32_t*>(ws + lay.slot_t);
+    a.msg_off = reinterpret_cast<uint64_t*>(ws + lay.msg_off);
+    a.msg_len = reinterpret_cast<uint64_t*>(ws + lay.msg_len);
+    a.blocks = reinterpret_cast<uint64_t*>(ws + lay.blocks);
+    a.flat = ws + lay.flat;
+    a.err = s->dev.err;
+    const int t = msha::env_int("MSHA_PARTS_PLAN_WAVE_SUM", (int)msha::parts_plan::kWaveSumParts);
+    a.wave_sum_parts = t < 1 ? 1u : (uint32_t)t;
+
+    // under MSHA_PARTS_TIMING=1 the claim counters are read back too, which makes the call wait
+    msha::LaunchTimer timer(st, !capturing && msha::LaunchTimer::wanted());
+    msha::launch_check(msha::launch_sroute_init(a, st), "k_sroute_init launch");
+    msha::launch_check(msha::launch_sroute_measure(a, st), "k_sroute_measure launch");
+    msha::launch_check(msha::launch_sroute_copy(a, st), "k_sroute_copy launch");
+    msha::launch_check(msha::launch_absorb_chain8(s->rows.state, a.flat, a.msg_off, a.blocks, a.slot_stream,
+                                                  a.max_long, s->dev.err, st),
+                       "k_absorb_chain8 launch");
+    msha::ctx_count_launch(s->ctx, msha::kLaunchChain8);
+    msha::launch_check(msha::launch_sroute_tail(a, st), "k_sroute_tail launch");
+    msha::launch_check(msha::launch_dstream_write_rest(a, st), "k_dstream_write_rest launch");
+    rs.ran = true;
+    rs.last_slots = a.max_long;
+    rs.at_row = lay.slot_row;
+    rs.at_stream = lay.slot_stream;
+    rs.at_claim = lay.claim;
+    if (!capturing) HIPCHK(hipEventRecord(rs.last, st));
+
+    const float ms = timer.stop();
+    unsigned long long claim[msha::parts_route::kClaimWords] = {};
+    if (timer.enabled()) HIPCHK(hipMemcpy(claim, a.claim, sizeof claim, hipMemcpyDeviceToHost));
+    msha_dstreams_route_stats& c = rs.st;
+    c.calls++;
+    c.rows += n_rows;
+    c.launches_route += 2;
+    c.launches_copy++;
+    c.launches_chain++;
+    c.launches_tail++;
+    c.launches_write++;
+    c.last_routed = claim[msha::parts_route::kClaimRouted];
+    c.last_routed_bytes = claim[msha::parts_route::kClaimBytes];
+    c.last_kernel_ms = ms;
+  });
+}
+
+int msha_dstreams_get_route_stats(const msha_dstreams* s, msha_dstreams_route_stats* out) {
+  if (!s || !out) return MSHA_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
+  *out = s->route.st;
+  return MSHA_OK;
+}
+
+int msha_dstreams_route_read(msha_dstreams* s, uint32_t* rows, uint64_t cap, uint64_t* n_routed,
+                             uint64_t* routed_bytes) {
+  if (!s || !n_routed || !routed_bytes || (cap && !rows)) return MSHA_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
+  *n_routed = *routed_bytes = 0;
+  const DstreamRoute& rs = s->route;
+  if (!rs.ran) return MSHA_OK;
+  return msha::guard(s->ctx, [&] {
+    HIPCHK(hipSetDevice(s->dev.id));
+    HIPCHK(hipDeviceSynchronize());
+    const uint8_t* ws = static_cast<const uint8_t*>(rs.ws);
+    const uint64_t m = rs.last_slots;
+    std::vector<uint32_t> row(m), strm(m);
+    unsigned long long claim[msha::parts_route::kClaimWords] = {};
+    HIPCHK(hipMemcpy(row.data(), ws + rs.at_row, 4 * m, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(strm.data(), ws + rs.at_stream, 4 * m, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(claim, ws + rs.at_claim, sizeof claim, hipMemcpyDeviceToHost));
+    uint64_t k = 0;
+    for (uint64_t j = 0; j < m; ++j) {
+      if (strm[j] == msha::schain::kNoStream) continue;  // a slot nobody filled
+      if (k < cap) rows[k] = row[j];
+      ++k;
+    }
+    *n_routed = k;
+    *routed_bytes = claim[msha::parts_route::kClaimBytes];
   });
 }
 

@@ -401,6 +401,21 @@ int msha_absorb_device(msha_ctx* ctx, uint32_t* d_state, const uint8_t* d_arena,
   });
 }
 
+int msha_absorb_chain_device(msha_ctx* ctx, uint32_t* d_state, const uint8_t* d_arena, const uint64_t* d_off,
+                             const uint64_t* d_nblocks, uint64_t n, void* stream) {
+  if (!ctx) return MSHA_ERR_INVALID_ARG;
+  if (n == 0) return MSHA_OK;
+  std::lock_guard<std::mutex> lock(msha::ctx_mutex(ctx));
+  if (!d_state || !d_arena || !d_off || !d_nblocks) return msha::ctx_fail(ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
+  return msha::guard(ctx, [&] {
+    msha::CtxDevice d;
+    const hipStream_t st = msha::device_entry(ctx, "msha_absorb_chain_device", stream, &d);
+    msha::launch_check(msha::launch_absorb_chain8(d_state, d_arena, d_off, d_nblocks, nullptr, n, d.err, st),
+                       "k_absorb_chain8 launch");
+    msha::ctx_count_launch(ctx, msha::kLaunchChain8);
+  });
+}
+
 int msha_finish_device(msha_ctx* ctx, const uint32_t* d_state, const uint64_t* d_prefix, const uint8_t* d_arena,
                        const uint64_t* d_off, const uint64_t* d_len, uint64_t n, uint8_t* d_out, void* stream) {
   if (!ctx) return MSHA_ERR_INVALID_ARG;

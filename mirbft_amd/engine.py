@@ -298,6 +298,14 @@ class Engine:
         self._check(self._lib.msha_absorb_device(self._ctx, state.data_ptr(), arena.data_ptr(), off.data_ptr(),
                                                  nblocks.data_ptr(), off.numel(), self._stream_ptr(stream)))
 
+    def absorb_chain_device(self, state, arena, off, nblocks, stream=None) -> None:
+        """msha_absorb_chain_device: absorb_device's arguments, rules and result on the
+        eight-lane chain kernel -- eight GPU lanes a lane, for few, long lanes."""
+        self._check_device_args(off.numel(), None, state=state, arena=arena, off=off, nblocks=nblocks)
+        self._check(self._lib.msha_absorb_chain_device(self._ctx, state.data_ptr(), arena.data_ptr(),
+                                                       off.data_ptr(), nblocks.data_ptr(), off.numel(),
+                                                       self._stream_ptr(stream)))
+
     def finish_device(self, state, prefix, arena, off, length, out, stream=None) -> None:
         """msha_finish_device: out[i] = the digest of the message whose first prefix[i]
         bytes are in state[i] (None: the initial value, prefix None: 0) and whose last

@@ -10,7 +10,9 @@ is one kernel launch on the caller's stream with no host wait, so a sequence of 
 captures into a HIP graph. ``write_jobs_device`` is ``StreamSet.write``'s job list in
 device memory -- jobs in call order, a stream named any number of times -- grouped by
 stream on the GPU inside the call: several launches, still on the caller's stream and
-capturable once its workspace exists. The device calls take torch tensors (``torch`` supplies
+capturable once its workspace exists. ``write_routed_device`` is ``write_device`` with the
+rows that compress many blocks found on the GPU and run on the eight-lane chain, eight
+lanes a stream instead of one. The device calls take torch tensors (``torch`` supplies
 device memory and streams only); ``lengths``, ``export_state`` and ``import_state``
 are synchronous and use numpy, in the layout ``StreamSet`` exports.
 """
@@ -124,6 +126,60 @@ class DeviceStreamSet:
         self._check(self._lib.msha_dstreams_write_device(
             self._handle(), arena.data_ptr(), part_off.data_ptr(), part_len.data_ptr(), row_part_begin.data_ptr(),
             self._ptr(rows), n_rows, Engine._stream_ptr(stream)))
+
+    def write_routed_device(self, arena, part_off, part_len, row_part_begin, rows=None, stream=None,
+                            long_blocks: int = 0, max_long: int = 0, long_bytes: int = 0) -> None:
+        """write_device with its long rows found on the GPU inside the call and run on the
+        eight-lane chain: a row whose write compresses long_blocks 64-byte blocks or more
+        is flattened behind its stream's buffered bytes into a buffer of the set's and
+        absorbed with eight lanes; the others are lanes as in write_device. At most
+        max_long rows and long_bytes bytes are routed, and a row that finds no slot or no
+        room stays a lane. 0 takes a default (64 blocks, 16 x compute units, 32 MiB).
+        State, buffer, length, errors and arena rules are write_device's; six launches,
+        all on ``stream``."""
+        self._check_tensors(arena=arena, part_off=part_off, part_len=part_len, row_part_begin=row_part_begin,
+                            rows=rows)
+        n_rows = self._n_rows(rows)
+        if row_part_begin.numel() != n_rows + 1:
+            raise ValueError(f"row_part_begin has {row_part_begin.numel()} entries, expected {n_rows + 1}")
+        if part_len.numel() != part_off.numel():
+            raise ValueError(f"part_len has {part_len.numel()} entries, part_off {part_off.numel()}")
+        if arena.data_ptr() % L.MSHA_DEVICE_ALIGN:
+            raise ValueError(f"arena must start on a {L.MSHA_DEVICE_ALIGN}-byte boundary")
+        for name, v, top in (("long_blocks", long_blocks, 1 << 32), ("max_long", max_long, 1 << 32),
+                             ("long_bytes", long_bytes, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise ValueError(f"{name} must be in [0, 2^{top.bit_length() - 1})")
+        if n_rows == 0:
+            return
+        opts = L.MshaRouteOpts(int(long_blocks), int(max_long), int(long_bytes))
+        if arena.numel() == 0:          # nothing to read: an empty tensor has no address to pass
+            arena = row_part_begin.new_zeros(2)
+        if part_off.numel() == 0:       # every row has zero parts
+            part_off = part_len = row_part_begin.new_zeros(2)
+        self._check(self._lib.msha_dstreams_write_routed_device(
+            self._handle(), arena.data_ptr(), part_off.data_ptr(), part_len.data_ptr(), row_part_begin.data_ptr(),
+            self._ptr(rows), n_rows, ctypes.byref(opts), Engine._stream_ptr(stream)))
+
+    def route_stats(self) -> dict:
+        """The counters of write_routed_device (stats() and jobs_stats() count none of its
+        calls); last_routed, last_routed_bytes and last_kernel_ms only under
+        MSHA_PARTS_TIMING=1."""
+        s = L.MshaDstreamsRouteStats()
+        self._check(self._lib.msha_dstreams_get_route_stats(self._handle(), ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in L.MshaDstreamsRouteStats._fields_}
+
+    def routed_rows(self):
+        """(rows, bytes) of the last write_routed_device (waits for the device): the row
+        indices it routed, in no particular order, and the bytes of the flatten buffer
+        they were given. A diagnostic."""
+        n, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self._lib.msha_dstreams_route_read(self._handle(), None, 0, ctypes.byref(n), ctypes.byref(b)))
+        ids = np.empty(n.value, dtype=np.uint32)
+        if n.value:
+            self._check(self._lib.msha_dstreams_route_read(self._handle(), _p(ids, ctypes.c_uint32), ids.size,
+                                                           ctypes.byref(n), ctypes.byref(b)))
+        return ids[:n.value], b.value
 
     def write_jobs_device(self, arena, job_stream, job_off, job_len, stream=None) -> None:
         """StreamSet.write's job list in device memory: for j in call order, stream

@@ -5,6 +5,7 @@ recorder's shape, and kernel against kernel over tools/parts_bench.py's part lis
     python3 tools/dstream_bench.py recorder [--reps 7] [--out profiles/streams_device/recorder.jsonl]
     python3 tools/dstream_bench.py kernel   [--reps 7] [--out profiles/streams_device/kernel.jsonl]
     python3 tools/dstream_bench.py jobs     [--reps 7] [--out profiles/streams_device/jobs.jsonl]
+    python3 tools/dstream_bench.py long     [--reps 7] [--out profiles/streams_device/long.jsonl]
 
 recorder  `--streams` (65,536) streams each appending `--digests` (20) 32-byte digests that
           sit in HBM as rows of a digest table (NodeState.Apply's shape, recorder.go:348).
@@ -33,6 +34,15 @@ jobs      the recorder's shape as NodeState.Apply produces it: the `--streams` x
           The same again for one small call (64 streams x 20 digests): the launch-bound
           end. Every stream's digest of every route is checked against hashlib outside
           the timed window.
+long      write_routed_device against write_device, each a write + sum_device with one
+          synchronisation at the end, alternating in one process after a warm repetition of
+          each, the grouped CSR given, over streams x digests of 32 bytes: 4 x 8,192,
+          64 x 2,048, 256 x 512 (few long streams: NodeState.ActiveHash's shape) and
+          65,536 x 20 (no long row: what the routed call's extra launches cost). A gain or
+          a loss is named only where the medians differ by more than the two spreads
+          combined. Then the `long_blocks` sweep (8 .. 256) on 64 x 2,048 and on a mixed
+          shape (65,536 x 20 with 32 streams of 2,048 among them). Every stream's digest of
+          every route is checked against hashlib outside the timed window.
 Every figure is the median of `--reps` (>= 5) timed repetitions after warm ones, with
 (max - min) / median beside it. A sample of what was timed is checked against hashlib.
 A measurement, not a threshold. Needs the GPU; there is no fallback.
@@ -198,6 +208,75 @@ def jobs(a, build):
                 _jobs_shape(eng, 64, 20, a.reps, build, "small")]
 
 
+def _long_shape(eng, n, k, reps, build, label, long_blocks=(0,), big=None):
+    """n streams x k digests; big = (count, digests): that many streams take `digests` instead."""
+    import torch
+    from mirbft_amd import DeviceStreamSet
+    dev = torch.device("cuda:0")
+    per = np.full(n, k, dtype=np.int64)
+    if big:
+        per[np.linspace(0, n - 1, big[0]).astype(np.int64)] = big[1]
+    begin_h = np.concatenate([[0], np.cumsum(per)])
+    total = int(begin_h[-1])
+    g = torch.Generator(device=dev)
+    g.manual_seed(11)
+    table = torch.randint(0, 256, (total * 32 + 64,), dtype=torch.uint8, device=dev, generator=g)
+    part_off = torch.arange(total, dtype=torch.int64, device=dev) * 32
+    part_len = torch.full((total,), 32, dtype=torch.int64, device=dev)
+    begin = torch.from_numpy(begin_h).to(dev)
+    out = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+    host = table.cpu().numpy()
+    check = sorted(set([0, 1, n // 2, n - 1] + (np.linspace(0, n - 1, big[0]).astype(int).tolist() if big else [])))
+    want = {s: hashlib.sha256(host[32 * begin_h[s]: 32 * begin_h[s + 1]].tobytes()).digest() for s in check}
+    torch.cuda.synchronize()
+    lines = []
+    with DeviceStreamSet(eng, n) as ds:
+        for lb in long_blocks:
+            routes = (("lanes", lambda: ds.write_device(table, part_off, part_len, begin)),
+                      ("routed", lambda: ds.write_routed_device(table, part_off, part_len, begin, long_blocks=lb)))
+            times = {"lanes": [], "routed": []}
+            for rep in range(reps + 1):                # the first of each is the warm one
+                for name, route in routes:
+                    ds.reset_device()
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    route()
+                    ds.sum_device(out)
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    got = out.cpu().numpy()
+                    for s_, w in want.items():
+                        assert got[s_].tobytes() == w, (label, name, lb, rep, s_)
+                    if rep:
+                        times[name].append((t1 - t0) * 1e3)
+            eng.device_status()
+            routed_rows, routed_bytes = ds.routed_rows()
+            a_, b_ = _stat(times["lanes"]), _stat(times["routed"])
+            spreads = (a_["max"] - a_["min"]) + (b_["max"] - b_["min"])
+            gap = a_["median"] - b_["median"]
+            lines.append({"measure": "long", "shape": label, "streams": n, "digests_per_stream": k,
+                          "big": list(big) if big else None, "bytes": total * 32, "reps": reps,
+                          "long_blocks": lb or "default", "routed_rows": int(routed_rows.size),
+                          "routed_bytes": int(routed_bytes), "write_device_ms": a_, "write_routed_ms": b_,
+                          "lanes_over_routed": round(a_["median"] / b_["median"], 3), "gap_ms": round(gap, 4),
+                          "spreads_combined_ms": round(spreads, 4),
+                          "routed_faster_by_more_than_the_spreads": bool(gap > spreads),
+                          "routed_slower_by_more_than_the_spreads": bool(-gap > spreads), "build": build["id"]})
+    return lines
+
+
+def long_rows(a, build):
+    from mirbft_amd import Engine
+    sweep = (8, 16, 32, 64, 128, 256)
+    with Engine(1) as eng:
+        lines = []
+        for label, n, k in (("a", 4, 8192), ("b", 64, 2048), ("c", 256, 512), ("d", 1 << 16, 20)):
+            lines += _long_shape(eng, n, k, a.reps, build, label)
+        lines += _long_shape(eng, 64, 2048, a.reps, build, "b_sweep", sweep)
+        lines += _long_shape(eng, 1 << 16, 20, a.reps, build, "mixed_sweep", sweep, big=(32, 2048))
+        return lines
+
+
 def _blocks(length):
     length = length.astype(np.uint64)
     return (length >> np.uint64(6)) + np.where((length & np.uint64(63)) < 56, 1, 2).astype(np.uint64)
@@ -281,7 +360,7 @@ def kernel(a, build):
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("measure", choices=["recorder", "kernel", "jobs"])
+    ap.add_argument("measure", choices=["recorder", "kernel", "jobs", "long"])
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--streams", type=int, default=1 << 16)
     ap.add_argument("--digests", type=int, default=20)
@@ -299,7 +378,7 @@ def main() -> int:
         ap.error("%s measures enqueue-only calls: unset MSHA_PARTS_TIMING" % a.measure)
     from mirbft_amd import _lib
     build = _lib.require_tree_build("dstream_bench")
-    lines = {"recorder": recorder, "kernel": kernel, "jobs": jobs}[a.measure](a, build)
+    lines = {"recorder": recorder, "kernel": kernel, "jobs": jobs, "long": long_rows}[a.measure](a, build)
     for ln in lines:
         print(json.dumps(ln))
     if a.out:

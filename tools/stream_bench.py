@@ -2,6 +2,7 @@
 """Rate of the stream sets' absorb kernel against the lane kernel, kernel-resident.
 
     python3 tools/stream_bench.py [--reps 7] [--lanes 1048576] [--out profiles/streams/bench.jsonl]
+    python3 tools/stream_bench.py --chain [--reps 7] [--out profiles/streams_device/long.jsonl]
 
 Two cases over the same device arena of `lanes` x 512 bytes, alternated in one
 process, each timed with HIP events (warm-up repetitions for 300 ms, then `reps` timed ones; a
@@ -10,6 +11,10 @@ enqueue time hides behind the kernel before it and is paid once a repetition):
   absorb  msha_absorb_device, 8 whole blocks a lane
   lane    msha_digest_batch_device, 512-byte messages: 9 blocks a lane (8 + padding);
           the yardstick, untouched by the stream sets
+--chain: msha_absorb_chain_device (eight lanes a stream) against msha_absorb_device (one)
+at 4, 64, 1,024 and 4,096 lanes of 1,024 blocks each, one launch between a pair of events,
+in ns per block of the launch (launch time / (lanes x blocks)); the states of both are
+compared. It shows where eight lanes a stream stop paying. A case line each, no verdict.
 Prints one JSON line a case (ns per lane-block of every repetition, the median and
 (max - min) / median) and a verdict line: absorb's per-block median should be no
 worse than the lane kernel's by more than the larger of the two spreads. The
@@ -31,8 +36,60 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 IV = [0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19]
 
 
+def chain_cases(a, build):
+    import torch
+    from mirbft_amd import Engine
+    dev = torch.device("cuda:0")
+    blocks = 1024
+    stream = torch.cuda.Stream(dev)
+    lines = []
+    with Engine(1) as eng:
+        for n in (4, 64, 1024, 4096):
+            g = torch.Generator(device=dev)
+            g.manual_seed(6)
+            arena = torch.randint(0, 256, (n * blocks * 64 + 64,), dtype=torch.uint8, device=dev, generator=g)
+            off = torch.arange(n, dtype=torch.int64, device=dev) * (blocks * 64)
+            nblocks = torch.full((n,), blocks, dtype=torch.int64, device=dev)
+            iv = torch.from_numpy(np.tile(np.array(IV, dtype=np.uint32), (n, 1)).view(np.int32)).to(dev)
+            states = {"chain": iv.clone(), "lane": iv.clone()}
+            fns = {"chain": eng.absorb_chain_device, "lane": eng.absorb_device}
+            times = {"chain": [], "lane": []}
+            torch.cuda.synchronize()
+            t_start, rep, warm = time.perf_counter(), 0, 0
+            while rep < a.reps:                    # warm-up repetitions first (at least one), untimed
+                warming = warm == 0 or (time.perf_counter() - t_start) * 1e3 < a.min_warmup_ms
+                if warming and rep == 0:
+                    warm += 1
+                else:
+                    rep += 1
+                for name in ("chain", "lane"):
+                    with torch.cuda.stream(stream):
+                        states[name].copy_(iv)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(stream)
+                    fns[name](states[name], arena, off, nblocks, stream=stream)
+                    e1.record(stream)
+                    e1.synchronize()
+                    if rep:
+                        times[name].append(e0.elapsed_time(e1))
+            eng.device_status()
+            assert torch.equal(states["chain"], states["lane"]), n
+            row = {"case": "chain", "lanes": n, "blocks_per_lane": blocks, "reps": a.reps, "warmup_reps": warm,
+                   "build": build["id"]}
+            for name in ("chain", "lane"):
+                per = [t * 1e6 / (n * blocks) for t in times[name]]
+                med = statistics.median(per)
+                row[name + "_ms"] = [round(t, 4) for t in times[name]]
+                row[name + "_median_ns_per_block"] = round(med, 4)
+                row[name + "_spread"] = round((max(per) - min(per)) / med, 4)
+            row["lane_over_chain"] = round(row["lane_median_ns_per_block"] / row["chain_median_ns_per_block"], 3)
+            lines.append(row)
+    return lines
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--chain", action="store_true", help="the eight-lane absorb chain against the lane absorb")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--lanes", type=int, default=1 << 20)
     ap.add_argument("--inner", type=int, default=8, help="launches between one pair of events")
@@ -45,6 +102,16 @@ def main() -> int:
     import torch
     from mirbft_amd import Engine, _lib
     build = _lib.require_tree_build("stream_bench")
+    if a.chain:
+        lines = chain_cases(a, build)
+        for ln in lines:
+            print(json.dumps(ln))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                for ln in lines:
+                    f.write(json.dumps(ln) + "\n")
+        return 0
     dev = torch.device("cuda:0")
     n, msg = a.lanes, 512
     g = torch.Generator(device=dev)
