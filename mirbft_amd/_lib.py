@@ -376,8 +376,8 @@ def lib() -> ctypes.CDLL:
 # The files msha_build_id()'s src hash covers, in the Makefile's order (SRCS).
 _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mirsha.cpp",
               os.path.join("..", "..", "include", "mirsha.h"),
-              "stream_kernels.hip", "stream_pack.hpp", "ctx_access.hpp", "host_call.hpp", "stream_state.hpp",
-              "streams.cpp",
+              "stream_kernels.hip", "stream_pack.hpp", "ctx_access.hpp", "host_call.hpp", "workspace_rule.hpp",
+              "call_workspace.hpp", "stream_state.hpp", "streams.cpp",
               "parts_gather.hpp", "parts_kernels.hip", "parts.cpp",
               "parts_digest.hpp", "parts_plan.hpp", "parts_plan.hip", "parts_plan.cpp",
               "parts_route.hpp", "parts_route.cpp",

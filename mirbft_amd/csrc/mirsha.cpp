@@ -34,6 +34,7 @@
 #include "kernels.hpp"
 #include "ctx_access.hpp"
 #include "host_call.hpp"
+#include "call_workspace.hpp"
 
 namespace {
 
@@ -2592,8 +2593,8 @@ void msha_ctx_destroy(msha_ctx* ctx) {
     for (hipStream_t st : {d.stream, d.copy_stream, d.d2h_stream})
       if (st) (void)hipStreamSynchronize(st);
     if (&d == &ctx->devs[0]) {  // their workspaces live on the first device
-      ctx->parts_plan.release();
-      ctx->parts_route.release();
+      ctx->parts_plan.ws.release();
+      ctx->parts_route.ws.release();
     }
     d.release();
   }

@@ -11,9 +11,8 @@
 #include <vector>
 
 #include "../../include/mirsha.h"
-#include "host_call.hpp"
+#include "call_workspace.hpp"
 #include "parts_concat.hpp"
-#include "parts_plan.hpp"
 
 extern "C" {
 
@@ -54,8 +53,7 @@ int msha_concat_lists_device(msha_ctx* ctx, const uint8_t* d_arena, const uint64
     a.msg_off = d_msg_off;
     a.msg_len = d_msg_len;
     a.err = d.err;
-    const int t = msha::env_int("MSHA_PARTS_PLAN_WAVE_SUM", (int)msha::parts_plan::kWaveSumParts);
-    a.wave_sum_parts = t < 1 ? 1u : (uint32_t)t;
+    a.wave_sum_parts = msha::wave_sum_parts();
     // MSHA_CONCAT_SCAN_ONLY (diagnostic, tools/parts_concat_bench.py), read at each call:
     // 1 stops after the scan, so measure and scan can be timed without the copy; 2 runs
     // the scan alone, over whatever d_msg_len and d_msg_off (the flags) hold. No byte of

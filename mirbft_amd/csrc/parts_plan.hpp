@@ -8,9 +8,12 @@
 // is the longest class -- so bucket starts are a plain prefix sum over the keys.
 //
 // This header compiles for the host as well: tests/cpp/parts_plan_key_check.cpp runs
-// it under AddressSanitizer + UBSan against a restatement.
+// it under AddressSanitizer + UBSan against a restatement, and
+// tests/cpp/call_workspace_check.cpp the workspace layout.
 #pragma once
 #include <stdint.h>
+
+#include "workspace_rule.hpp"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define MSHA_PLAN_HD __host__ __device__ __forceinline__
@@ -48,6 +51,23 @@ MSHA_PLAN_HD uint32_t class_key(uint64_t blocks) {
   if (blocks >= kExactBlocks) return 63u - log2_floor(blocks);
   return kBigClasses + (kExactBlocks - 1u) - (uint32_t)blocks;
 }
+
+// The workspace of a call over n lists (n < 2^32), byte offsets from its base: info (16
+// words) and the counters, one array to k_parts_init, lie at 0; then the order, at an
+// offset that does not depend on n (msha_parts_plan_read_order reads it after the call);
+// then the keys, the used flags and the digest table. at: where the order lies -- behind
+// the counters, or behind what another entry puts between them (parts_route.hpp Layout).
+MSHA_HD uint64_t head_bytes() { return round64(4ull * (16 + kKeys)); }
+struct Layout {
+  uint64_t order, key16, used, table, bytes;
+  MSHA_HD Layout(uint64_t n, bool with_list, uint64_t at = head_bytes()) {
+    order = at;
+    key16 = order + round64(4 * n);
+    used = key16 + round64(2 * n);
+    table = used + (with_list ? round64(n) : 0);
+    bytes = table + (with_list ? 32 * n : 0) + 64;
+  }
+};
 
 }  // namespace parts_plan
 }  // namespace msha

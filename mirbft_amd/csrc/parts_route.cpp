@@ -12,7 +12,8 @@
 //   k_digest_parts_planned, k_parts_fill       the lanes that remain
 // The lengths come out of the measure, so k_concat_measure and k_concat_scan do not run:
 // a list's parts are summed once a call. The workspace is this entry's own
-// (ctx_access.hpp PartsRouteState) and grows only outside stream capture.
+// (call_workspace.hpp PartsRouteState, laid out by parts_route.hpp Layout) and follows
+// the workspace rule stated there.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -20,37 +21,12 @@
 #include <vector>
 
 #include "../../include/mirsha.h"
-#include "host_call.hpp"
-#include "parts_plan.hpp"
+#include "call_workspace.hpp"
 #include "parts_route.hpp"
 
 namespace {
 
 const char* const kEntry = "msha_hash_actions_device_routed";
-
-uint64_t round64(uint64_t x) { return (x + 63) & ~uint64_t(63); }
-uint64_t round256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
-
-// The workspace of a call over n lists with m slots and a flatten buffer of `flat_bytes`:
-// info and the counters, one array to k_route_init; the claim counters; the slots' five
-// arrays; the planned call's order, keys, used flags and digest table; the buffer.
-struct Layout {
-  uint64_t claim, msg_off, msg_len, sel, chain, out_idx, order, key16, used, table, flat, bytes;
-  Layout(uint64_t n, uint64_t m, uint64_t flat_bytes, bool with_list) {
-    claim = round64(4ull * (16 + msha::parts_plan::kKeys));
-    msg_off = claim + round64(8ull * msha::parts_route::kClaimWords);
-    msg_len = msg_off + round64(8 * m);
-    sel = msg_len + round64(8 * m);
-    chain = sel + round64(4 * m);
-    out_idx = chain + round64(4 * m);
-    order = out_idx + round64(4 * m);
-    key16 = order + round64(4 * n);
-    used = key16 + round64(2 * n);
-    table = used + (with_list ? round64(n) : 0);
-    flat = round256(table + (with_list ? 32 * n : 0) + 64);
-    bytes = flat + flat_bytes;
-  }
-};
 
 }  // namespace
 
@@ -69,13 +45,9 @@ int msha_hash_actions_device_routed(msha_ctx* ctx, const uint8_t* d_arena, const
                                           std::to_string(n_actions) + ") must equal n_lists (" +
                                           std::to_string(n_lists) + ")");
   if (n_actions == 0) return MSHA_OK;  // before opts, whose max_long bound needs the device
-  const msha_route_opts o = opts ? *opts : msha_route_opts{0, 0, 0};
-  if (o.long_bytes != 0 && o.long_bytes < 16 + MSHA_DEVICE_ARENA_SLACK)
-    return msha::bad_arg(ctx, kEntry, "opts->long_bytes (" + std::to_string(o.long_bytes) +
-                                          ") holds no list: it must be 0 or at least " +
-                                          std::to_string(16 + MSHA_DEVICE_ARENA_SLACK));
-  if (o.long_bytes > (1ull << 48))
-    return msha::bad_arg(ctx, kEntry, "opts->long_bytes (" + std::to_string(o.long_bytes) + ") is above 2^48");
+  // opts: the long_bytes bounds here, the max_long bound once the device is known
+  const int rc = msha::guard(ctx, [&] { (void)msha::route_opts(kEntry, "list", opts, 0, MSHA_ROUTE_LONG_BLOCKS_DEFAULT); });
+  if (rc != MSHA_OK) return rc;
   if (!d_arena || !d_part_off || !d_part_len || !d_list_part_begin || !d_out)
     return msha::ctx_fail(ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
   if (reinterpret_cast<uintptr_t>(d_arena) % MSHA_DEVICE_ALIGN)
@@ -86,63 +58,21 @@ int msha_hash_actions_device_routed(msha_ctx* ctx, const uint8_t* d_arena, const
     // device call would make one (the error word) or the workspace would grow
     const bool capturing = stream && msha::stream_capturing(static_cast<hipStream_t>(stream));
     msha::PartsRouteState& rs = msha::ctx_parts_route(ctx);
-    const char* const no_growth =
-        ": the workspace cannot grow while the stream is being captured: "
-        "make one call of this size outside the capture first";
-    if (capturing && !msha::ctx_first_device_ready(ctx))
-      throw msha::MshaError(MSHA_ERR_INVALID_ARG, std::string(kEntry) + no_growth);
+    if (capturing && !msha::ctx_first_device_ready(ctx)) msha::CallWorkspace::refuse(kEntry);
     msha::CtxDevice d;
     const hipStream_t st = msha::device_entry(ctx, kEntry, stream, capturing, &d);
 
-    // the slots are lanes of the eight-lane chain, one workgroup a CU
-    const uint64_t most = (uint64_t)d.cus * msha::kChain8MsgsPerWg;
-    if (o.max_long > most)
-      throw msha::MshaError(MSHA_ERR_INVALID_ARG, std::string(kEntry) + ": opts->max_long (" +
-                                                      std::to_string(o.max_long) + ") is above 16 x compute units (" +
-                                                      std::to_string(most) + ")");
+    const msha_route_opts o = msha::route_opts(kEntry, "list", opts, d.cus, MSHA_ROUTE_LONG_BLOCKS_DEFAULT);
     msha::RouteArgs r;
-    r.long_blocks = o.long_blocks ? o.long_blocks : MSHA_ROUTE_LONG_BLOCKS_DEFAULT;
-    r.max_long = o.max_long ? o.max_long : (uint32_t)most;
-    r.long_bytes = o.long_bytes ? o.long_bytes : MSHA_ROUTE_LONG_BYTES_DEFAULT;
+    r.long_blocks = o.long_blocks;
+    r.max_long = o.max_long;
+    r.long_bytes = o.long_bytes;
 
-    const Layout lay(n_lists, r.max_long, r.long_bytes, d_action_list != nullptr);
-    if (capturing && lay.bytes > rs.ws_bytes)
-      throw msha::MshaError(MSHA_ERR_INVALID_ARG, std::string(kEntry) + no_growth);
-    if (lay.bytes > rs.ws_bytes) {
-      // an earlier call may still be using the old buffer
-      if (rs.last) HIPCHK(hipEventSynchronize(rs.last));
-      if (rs.ws) HIPCHK(hipFree(rs.ws));
-      rs.ws = nullptr;
-      rs.ws_bytes = 0;
-      rs.ran = false;
-      // the arrays grow with a quarter to spare, the flatten buffer is what was asked for
-      const uint64_t want = lay.bytes + lay.flat / 4;
-      HIPCHK(hipMalloc(&rs.ws, want));
-      rs.ws_bytes = want;
-    }
-    if (!rs.last && !capturing) HIPCHK(hipEventCreateWithFlags(&rs.last, hipEventDisableTiming));
-    // two streams must not race on the workspace: after the previous call's last kernel
-    if (!capturing && rs.ran) HIPCHK(hipStreamWaitEvent(st, rs.last, 0));
-
-    uint8_t* ws = static_cast<uint8_t*>(rs.ws);
-    msha::PartsPlanArgs a;
-    a.arena = d_arena;
-    a.part_off = d_part_off;
-    a.part_len = d_part_len;
-    a.begin = d_list_part_begin;
-    a.n_lists = n_lists;
-    a.action_list = d_action_list;
-    a.n_actions = n_actions;
-    a.info = reinterpret_cast<uint32_t*>(ws);
-    a.cnt = a.info + 16;
-    a.order = reinterpret_cast<uint32_t*>(ws + lay.order);
-    a.key16 = reinterpret_cast<uint16_t*>(ws + lay.key16);
-    a.used = d_action_list ? ws + lay.used : nullptr;
-    a.table = d_action_list ? ws + lay.table : nullptr;
-    a.out = d_out;
-    a.err = d.err;
-    const int t = msha::env_int("MSHA_PARTS_PLAN_WAVE_SUM", (int)msha::parts_plan::kWaveSumParts);
-    a.wave_sum_parts = t < 1 ? 1u : (uint32_t)t;
+    const msha::parts_route::Layout lay(n_lists, r.max_long, r.long_bytes, d_action_list != nullptr);
+    // the arrays grow with a quarter to spare, the flatten buffer is what was asked for
+    uint8_t* ws = rs.ws.acquire(kEntry, lay.bytes, lay.flat / 4, capturing, st);
+    const msha::PartsPlanArgs a = msha::plan_args(d_arena, d_part_off, d_part_len, d_list_part_begin, n_lists,
+                                                  d_action_list, n_actions, d_out, d.err, ws, lay.plan);
     r.claim = reinterpret_cast<unsigned long long*>(ws + lay.claim);
     r.msg_off = reinterpret_cast<uint64_t*>(ws + lay.msg_off);
     r.msg_len = reinterpret_cast<uint64_t*>(ws + lay.msg_len);
@@ -180,14 +110,13 @@ int msha_hash_actions_device_routed(msha_ctx* ctx, const uint8_t* d_arena, const
     msha::ctx_count_launch(ctx, kind);
     msha::launch_check(msha::launch_digest_parts_planned(a, st), "k_digest_parts_planned launch");
     if (d_action_list) msha::launch_check(msha::launch_parts_fill(a, st), "k_parts_fill launch");
-    rs.ran = true;
     rs.last_lists = n_lists;
     rs.last_slots = r.max_long;
-    rs.at_order = lay.order;
+    rs.at_order = lay.plan.order;
     rs.at_chain = lay.chain;
     rs.at_out_idx = lay.out_idx;
     rs.at_claim = lay.claim;
-    if (!capturing) HIPCHK(hipEventRecord(rs.last, st));
+    rs.ws.commit(st, capturing);
 
     const float ms = timer.stop();
     uint32_t info[4] = {0, 0, 0, 0};
@@ -227,11 +156,11 @@ int msha_parts_route_read(msha_ctx* ctx, uint32_t* lists, uint64_t cap, uint64_t
   msha::PartsRouteState& rs = msha::ctx_parts_route(ctx);
   *n_routed = 0;
   *routed_bytes = 0;
-  if (!rs.ran) return MSHA_OK;
+  if (!rs.ws.ran()) return MSHA_OK;
   return msha::guard(ctx, [&] {
     (void)msha::ctx_first_device(ctx);
     HIPCHK(hipDeviceSynchronize());
-    const uint8_t* ws = static_cast<const uint8_t*>(rs.ws);
+    const uint8_t* ws = rs.ws.data();
     const uint64_t m = rs.last_slots;
     std::vector<uint32_t> chain(m), idx(m);
     unsigned long long claim[msha::parts_route::kClaimWords] = {};
@@ -253,19 +182,7 @@ int msha_parts_route_read_order(msha_ctx* ctx, uint32_t* order, uint64_t cap, ui
   if (!ctx || !lanes || (cap && !order)) return MSHA_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(ctx));
   msha::PartsRouteState& rs = msha::ctx_parts_route(ctx);
-  *lanes = 0;
-  if (!rs.ran) return MSHA_OK;
-  return msha::guard(ctx, [&] {
-    (void)msha::ctx_first_device(ctx);
-    HIPCHK(hipDeviceSynchronize());
-    const uint8_t* ws = static_cast<const uint8_t*>(rs.ws);
-    uint32_t n = 0;
-    HIPCHK(hipMemcpy(&n, ws, 4, hipMemcpyDeviceToHost));
-    if (n > rs.last_lists) n = (uint32_t)rs.last_lists;  // the order holds last_lists positions
-    *lanes = n;
-    const uint64_t k = n < cap ? n : cap;
-    if (k) HIPCHK(hipMemcpy(order, ws + rs.at_order, 4 * k, hipMemcpyDeviceToHost));
-  });
+  return msha::read_plan_order(ctx, rs.ws, rs.last_lists, rs.at_order, order, cap, lanes);
 }
 
 }  // extern "C"

@@ -13,11 +13,13 @@
 // kernel and a message of no bytes to the copy.
 //
 // This header compiles for the host as well: tests/cpp/parts_route_check.cpp drives it
-// under AddressSanitizer + UBSan.
+// under AddressSanitizer + UBSan, and tests/cpp/call_workspace_check.cpp the workspace
+// layout.
 #pragma once
 #include <stdint.h>
 
 #include "parts_concat.hpp"
+#include "parts_plan.hpp"
 
 namespace msha {
 namespace parts_route {
@@ -46,6 +48,27 @@ MSHA_HD bool room_ok(uint64_t given, uint64_t len, uint64_t long_bytes, uint64_t
   *next = given + parts_concat::round16(len);
   return true;
 }
+
+// The workspace of a call over n lists with m slots (n, m < 2^32) and a flatten buffer of
+// flat_bytes (<= 2^48: the sum stays far below 2^64), byte offsets from its base: info
+// and the counters, one array to k_route_init, lie at 0; the claim counters; the slots'
+// five arrays; the planned call's order, keys, used flags and digest table (plan, placed
+// behind the slots); the buffer. The members are initialised in this order.
+struct Layout {
+  uint64_t claim, msg_off, msg_len, sel, chain, out_idx;
+  parts_plan::Layout plan;
+  uint64_t flat, bytes;
+  MSHA_HD Layout(uint64_t n, uint64_t m, uint64_t flat_bytes, bool with_list)
+      : claim(parts_plan::head_bytes()),
+        msg_off(claim + round64(8ull * kClaimWords)),
+        msg_len(msg_off + round64(8 * m)),
+        sel(msg_len + round64(8 * m)),
+        chain(sel + round64(4 * m)),
+        out_idx(chain + round64(4 * m)),
+        plan(n, with_list, out_idx + round64(4 * m)),
+        flat(round256(plan.bytes)),
+        bytes(flat + flat_bytes) {}
+};
 
 }  // namespace parts_route
 }  // namespace msha

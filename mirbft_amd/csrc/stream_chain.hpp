@@ -106,9 +106,6 @@ MSHA_HD uint32_t tail_row_dword(uint32_t message_dword, uint32_t j, uint32_t rem
 // What an unfilled slot holds: no stream for the chain and the tail, no bytes for the copy.
 constexpr uint32_t kNoStream = 0xFFFFFFFFu;  // kernels.hpp kNoLane
 
-MSHA_HD uint64_t round64(uint64_t x) { return (x + 63) & ~uint64_t(63); }
-MSHA_HD uint64_t round256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
-
 // Byte offsets for a call of n_rows rows, m slots and a flatten buffer of flat_bytes
 // (n_rows < 2^32, m < 2^32, flat_bytes <= 2^48: the sum stays far below 2^64): the claim
 // words, a flag byte a row, six arrays a slot, the buffer.

@@ -13,9 +13,9 @@
 // msha_dstreams_write_routed_device: the rows whose write compresses many blocks are
 // found on the GPU, flattened behind their stream's buffered bytes and absorbed by the
 // eight-lane chain, the others written as lanes (stream_chain.hip, kernels.hip
-// k_absorb_chain8; six launches). Each workspace follows the rule of
-// msha_hash_actions_device_planned (parts_plan.cpp): it grows only outside stream
-// capture, and a call outside capture is ordered after the set's previous call of its kind.
+// k_absorb_chain8; six launches). Each workspace is a CallWorkspace and follows the
+// workspace rule stated in call_workspace.hpp: it grows only outside stream capture, and
+// a call outside capture is ordered after the set's previous call of its kind.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -24,20 +24,16 @@
 #include <vector>
 
 #include "../../include/mirsha.h"
-#include "host_call.hpp"
+#include "call_workspace.hpp"
 #include "stream_chain.hpp"
 #include "stream_device.hpp"
-#include "parts_plan.hpp"
 #include "stream_jobs.hpp"
 #include "stream_state.hpp"
 
 // The workspace of the jobs calls and what msha_dstreams_jobs_read_order needs of the
 // last one.
 struct DstreamJobs {
-  void* ws = nullptr;
-  uint64_t ws_bytes = 0;
-  hipEvent_t last = nullptr;  // recorded after the last call made outside capture
-  bool ran = false;
+  msha::CallWorkspace ws;
   uint64_t last_jobs = 0;
   uint32_t last_passes = 0;
   msha_dstreams_jobs_stats st{};
@@ -46,10 +42,7 @@ struct DstreamJobs {
 // The workspace of the routed writes (stream_chain.hpp Layout) and what
 // msha_dstreams_route_read needs of the last one.
 struct DstreamRoute {
-  void* ws = nullptr;
-  uint64_t ws_bytes = 0;
-  hipEvent_t last = nullptr;  // recorded after the last call made outside capture
-  bool ran = false;
+  msha::CallWorkspace ws;
   uint64_t last_slots = 0;
   uint64_t at_row = 0, at_stream = 0, at_claim = 0;  // byte offsets in ws of the last call's arrays
   msha_dstreams_route_stats st{};
@@ -85,10 +78,8 @@ void release(msha_dstreams* s) {
   if (s->rows.state) (void)hipFree(s->rows.state);
   if (s->rows.tail) (void)hipFree(s->rows.tail);
   if (s->rows.length) (void)hipFree(s->rows.length);
-  if (s->jobs.ws) (void)hipFree(s->jobs.ws);  // waits for the device
-  if (s->jobs.last) (void)hipEventDestroy(s->jobs.last);
-  if (s->route.ws) (void)hipFree(s->route.ws);  // waits for the device
-  if (s->route.last) (void)hipEventDestroy(s->route.last);
+  s->jobs.ws.release();
+  s->route.ws.release();
 }
 
 // The row arguments every device call shares. Call with the lock held.
@@ -228,29 +219,11 @@ int msha_dstreams_write_jobs_device(msha_dstreams* s, const uint8_t* d_arena, co
     // a capturing stream allows no allocation: know that before the workspace would grow
     const bool capturing = stream && msha::stream_capturing(static_cast<hipStream_t>(stream));
     DstreamJobs& js = s->jobs;
-    if (capturing && lay.bytes > js.ws_bytes)
-      throw msha::MshaError(MSHA_ERR_INVALID_ARG,
-                            std::string(kEntry) + ": the workspace cannot grow while the stream is being captured: "
-                                                  "make one call of this size outside the capture first");
+    js.ws.refuse_growth(kEntry, lay.bytes, capturing);
     msha::CtxDevice d;  // the set's own (s->dev): the context's first device
     const hipStream_t st = msha::device_entry(s->ctx, kEntry, stream, capturing, &d);
 
-    if (lay.bytes > js.ws_bytes) {
-      // an earlier call may still be using the old buffer
-      if (js.last && js.ran) HIPCHK(hipEventSynchronize(js.last));
-      if (js.ws) HIPCHK(hipFree(js.ws));
-      js.ws = nullptr;
-      js.ws_bytes = 0;
-      js.ran = false;
-      const uint64_t want = lay.bytes + lay.bytes / 4;
-      HIPCHK(hipMalloc(&js.ws, want));
-      js.ws_bytes = want;
-    }
-    if (!js.last && !capturing) HIPCHK(hipEventCreateWithFlags(&js.last, hipEventDisableTiming));
-    // two streams must not race on the workspace: after the previous call's last kernel
-    if (!capturing && js.ran && js.last) HIPCHK(hipStreamWaitEvent(st, js.last, 0));
-
-    uint8_t* ws = static_cast<uint8_t*>(js.ws);
+    uint8_t* ws = js.ws.acquire(kEntry, lay.bytes, lay.bytes / 4, capturing, st);
     msha::StreamJobsArgs a;
     a.job_stream = d_job_stream;
     a.job_off = d_job_off;
@@ -273,10 +246,9 @@ int msha_dstreams_write_jobs_device(msha_dstreams* s, const uint8_t* d_arena, co
     msha::launch_check(msha::launch_dstream_write(s->rows, d_arena, a.goff, a.glen, a.begin, nullptr, s->rows.n,
                                                   s->dev.err, st),
                        "k_dstream_write launch");
-    js.ran = true;
     js.last_jobs = n_jobs;
     js.last_passes = a.passes;
-    if (!capturing) HIPCHK(hipEventRecord(js.last, st));
+    js.ws.commit(st, capturing);
     const float ms = timer.stop();
     msha_dstreams_jobs_stats& t = js.st;
     t.calls++;
@@ -304,12 +276,12 @@ int msha_dstreams_jobs_read_order(msha_dstreams* s, uint32_t* order, uint64_t ca
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
   *n_jobs = *n_valid = 0;
   const DstreamJobs& js = s->jobs;
-  if (!js.ran) return MSHA_OK;
+  if (!js.ws.ran()) return MSHA_OK;
   return msha::guard(s->ctx, [&] {
     HIPCHK(hipSetDevice(s->dev.id));
     HIPCHK(hipDeviceSynchronize());
     const sj::Layout lay(js.last_jobs, s->rows.n);
-    const uint8_t* ws = static_cast<const uint8_t*>(js.ws);
+    const uint8_t* ws = js.ws.data();
     uint64_t valid = 0;
     HIPCHK(hipMemcpy(&valid, ws + lay.begin + 8 * s->rows.n, 8, hipMemcpyDeviceToHost));
     *n_jobs = js.last_jobs;
@@ -337,13 +309,11 @@ int msha_dstreams_write_routed_device(msha_dstreams* s, const uint8_t* d_arena, 
     return msha::bad_arg(s->ctx, kEntry, "d_arena must be 16-byte aligned");
   const int rc = check_rows(s, kEntry, d_row, n_rows);
   if (rc != MSHA_OK) return rc;
-  const msha_route_opts o = opts ? *opts : msha_route_opts{0, 0, 0};
-  if (o.long_bytes != 0 && o.long_bytes < 16 + MSHA_DEVICE_ARENA_SLACK)
-    return msha::bad_arg(s->ctx, kEntry, "opts->long_bytes (" + std::to_string(o.long_bytes) +
-                                             ") holds no row: it must be 0 or at least " +
-                                             std::to_string(16 + MSHA_DEVICE_ARENA_SLACK));
-  if (o.long_bytes > (1ull << 48))
-    return msha::bad_arg(s->ctx, kEntry, "opts->long_bytes (" + std::to_string(o.long_bytes) + ") is above 2^48");
+  // opts: the long_bytes bounds here, the max_long bound once the device is known
+  const int orc = msha::guard(s->ctx, [&] {
+    (void)msha::route_opts(kEntry, "row", opts, 0, MSHA_DSTREAMS_ROUTE_LONG_BLOCKS_DEFAULT);
+  });
+  if (orc != MSHA_OK) return orc;
 
   return msha::guard(s->ctx, [&] {
     // a capturing stream allows no allocation: know that before the workspace would grow
@@ -351,41 +321,17 @@ int msha_dstreams_write_routed_device(msha_dstreams* s, const uint8_t* d_arena, 
     msha::CtxDevice d;  // the set's own (s->dev): the context's first device
     const hipStream_t st = msha::device_entry(s->ctx, kEntry, stream, capturing, &d);
 
-    // the slots are lanes of the eight-lane chain, one workgroup a CU
-    const uint64_t most = (uint64_t)d.cus * msha::kChain8MsgsPerWg;
-    if (o.max_long > most)
-      throw msha::MshaError(MSHA_ERR_INVALID_ARG, std::string(kEntry) + ": opts->max_long (" +
-                                                      std::to_string(o.max_long) + ") is above 16 x compute units (" +
-                                                      std::to_string(most) + ")");
+    const msha_route_opts o = msha::route_opts(kEntry, "row", opts, d.cus, MSHA_DSTREAMS_ROUTE_LONG_BLOCKS_DEFAULT);
     msha::StreamRouteArgs a;
-    a.long_blocks = o.long_blocks ? o.long_blocks : MSHA_DSTREAMS_ROUTE_LONG_BLOCKS_DEFAULT;
-    a.max_long = o.max_long ? o.max_long : (uint32_t)most;
-    a.long_bytes = o.long_bytes ? o.long_bytes : MSHA_ROUTE_LONG_BYTES_DEFAULT;
+    a.long_blocks = o.long_blocks;
+    a.max_long = o.max_long;
+    a.long_bytes = o.long_bytes;
 
     DstreamRoute& rs = s->route;
     const sc::Layout lay(n_rows, a.max_long, a.long_bytes);
     if (!lay.ok) throw msha::MshaError(MSHA_ERR_INVALID_ARG, std::string(kEntry) + ": the workspace size does not fit");
-    if (capturing && lay.bytes > rs.ws_bytes)
-      throw msha::MshaError(MSHA_ERR_INVALID_ARG,
-                            std::string(kEntry) + ": the workspace cannot grow while the stream is being captured: "
-                                                  "make one call of this size outside the capture first");
-    if (lay.bytes > rs.ws_bytes) {
-      // an earlier call may still be using the old buffer
-      if (rs.last && rs.ran) HIPCHK(hipEventSynchronize(rs.last));
-      if (rs.ws) HIPCHK(hipFree(rs.ws));
-      rs.ws = nullptr;
-      rs.ws_bytes = 0;
-      rs.ran = false;
-      // the arrays grow with a quarter to spare, the flatten buffer is what was asked for
-      const uint64_t want = lay.bytes + lay.flat / 4;
-      HIPCHK(hipMalloc(&rs.ws, want));
-      rs.ws_bytes = want;
-    }
-    if (!rs.last && !capturing) HIPCHK(hipEventCreateWithFlags(&rs.last, hipEventDisableTiming));
-    // two streams must not race on the workspace: after the previous call's last kernel
-    if (!capturing && rs.ran && rs.last) HIPCHK(hipStreamWaitEvent(st, rs.last, 0));
-
-    uint8_t* ws = static_cast<uint8_t*>(rs.ws);
+    // the arrays grow with a quarter to spare, the flatten buffer is what was asked for
+    uint8_t* ws = rs.ws.acquire(kEntry, lay.bytes, lay.flat / 4, capturing, st);
     a.rows = s->rows;
     a.arena = d_arena;
     a.part_off = d_part_off;
@@ -403,8 +349,7 @@ int msha_dstreams_write_routed_device(msha_dstreams* s, const uint8_t* d_arena, 
     a.blocks = reinterpret_cast<uint64_t*>(ws + lay.blocks);
     a.flat = ws + lay.flat;
     a.err = s->dev.err;
-    const int t = msha::env_int("MSHA_PARTS_PLAN_WAVE_SUM", (int)msha::parts_plan::kWaveSumParts);
-    a.wave_sum_parts = t < 1 ? 1u : (uint32_t)t;
+    a.wave_sum_parts = msha::wave_sum_parts();
 
     // under MSHA_PARTS_TIMING=1 the claim counters are read back too, which makes the call wait
     msha::LaunchTimer timer(st, !capturing && msha::LaunchTimer::wanted());
@@ -417,12 +362,11 @@ int msha_dstreams_write_routed_device(msha_dstreams* s, const uint8_t* d_arena, 
     msha::ctx_count_launch(s->ctx, msha::kLaunchChain8);
     msha::launch_check(msha::launch_sroute_tail(a, st), "k_sroute_tail launch");
     msha::launch_check(msha::launch_dstream_write_rest(a, st), "k_dstream_write_rest launch");
-    rs.ran = true;
     rs.last_slots = a.max_long;
     rs.at_row = lay.slot_row;
     rs.at_stream = lay.slot_stream;
     rs.at_claim = lay.claim;
-    if (!capturing) HIPCHK(hipEventRecord(rs.last, st));
+    rs.ws.commit(st, capturing);
 
     const float ms = timer.stop();
     unsigned long long claim[msha::parts_route::kClaimWords] = {};
@@ -454,11 +398,11 @@ int msha_dstreams_route_read(msha_dstreams* s, uint32_t* rows, uint64_t cap, uin
   std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
   *n_routed = *routed_bytes = 0;
   const DstreamRoute& rs = s->route;
-  if (!rs.ran) return MSHA_OK;
+  if (!rs.ws.ran()) return MSHA_OK;
   return msha::guard(s->ctx, [&] {
     HIPCHK(hipSetDevice(s->dev.id));
     HIPCHK(hipDeviceSynchronize());
-    const uint8_t* ws = static_cast<const uint8_t*>(rs.ws);
+    const uint8_t* ws = rs.ws.data();
     const uint64_t m = rs.last_slots;
     std::vector<uint32_t> row(m), strm(m);
     unsigned long long claim[msha::parts_route::kClaimWords] = {};

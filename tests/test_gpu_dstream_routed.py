@@ -253,6 +253,47 @@ def test_rounds(engine):
         assert s.route_stats()["calls"] == 3 and _status(engine) == ""
 
 
+def test_workspace_grows_between_calls_on_two_streams(engine):
+    """A small routed write, one that must grow the set's workspace, the small one again,
+    alternating between two caller streams with no host wait between them; the sums
+    against hashlib. The set is fresh, so the first call allocates for 6 rows and a 4 KiB
+    buffer (under 5 KB with its spare) and the second needs 300 rows and 64 KiB: the old
+    buffer is freed under a call that may still be running."""
+    import torch
+    n = 300
+    rng = np.random.default_rng(0x6A0)
+    arena = rng.integers(0, 256, (1 << 16) + M.SLACK, dtype=np.uint8)
+
+    def batch(k, least, span):
+        """k rows of two parts, least .. least + span - 1 bytes a row: from 128 bytes a row is long at long_blocks 2."""
+        total = np.array([least + (37 * r) % span for r in range(k)], dtype=np.uint64)
+        first = total // 3
+        ln = np.stack([first, total - first], axis=1).reshape(-1)
+        off = rng.integers(0, (1 << 16) - 200, 2 * k).astype(np.uint64)
+        return arena, off, ln, np.arange(0, 2 * k + 1, 2, dtype=np.uint64)
+
+    few = np.array([7, 2, 299, 11, 5, 0], dtype=np.uint32)
+    calls = [(batch(few.size, 130, 60), few, 4 << 10), (batch(n, 40, 150), None, 64 << 10),
+             (batch(few.size, 130, 60), few, 4 << 10)]
+    assert all(sum(1 for r in range(b[3].size - 1) if int(b[2][2 * r] + b[2][2 * r + 1]) >= 128) > 4 for b, _, _ in calls)
+    dev = [([_dev(x) for x in b], None if rows is None else _dev(rows)) for b, rows, _ in calls]
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    out = torch.zeros((n, 32), dtype=torch.uint8, device="cuda:0")
+    with DeviceStreamSet(engine, n) as s:
+        fed = Bytes(n)
+        _sync()
+        for k, (b, rows, long_bytes) in enumerate(calls):
+            s.write_routed_device(*dev[k][0], rows=dev[k][1], stream=streams[k % 2], long_blocks=2, max_long=4,
+                                  long_bytes=long_bytes)
+            fed.write(b, rows)
+        _sync()
+        assert _status(engine) == "" and s.route_stats()["calls"] == 3
+        assert len(s.routed_rows()[0]) == 4                                  # the last call's: more long rows than slots
+        s.sum_device(out)
+        _sync()
+        assert [bytes(r) for r in out.cpu().numpy()] == [hashlib.sha256(d).digest() for d in fed.data]
+
+
 def test_capture(engine):
     """Refused with the jobs entry's text while the workspace is too small; after one call
     outside the capture, capture and two replays: the streams have appended three times."""

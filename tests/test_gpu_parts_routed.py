@@ -245,6 +245,35 @@ def test_calls_of_different_shapes_share_one_context(engine):
 
 
 @gpu
+def test_workspace_grows_between_calls_on_two_streams():
+    """A small call, one that must grow the workspace, the small one again, alternating
+    between two caller streams with no host wait between them. A fresh context, so the
+    first call allocates for 5 lists and a 4 KiB buffer (about 26 KB with its spare) and
+    the second needs 300 lists and 64 KiB: the old buffer is freed under a call that may
+    still be running, and the third call runs in the larger one at other offsets."""
+    import torch
+    from mirbft_amd import Engine
+    small = M.uniform(5, True, False)._replace(max_long=4, long_bytes=4 << 10)
+    large = M.uniform(300, True, False)._replace(max_long=4, long_bytes=64 << 10)
+    assert small.long_blocks == large.long_blocks == 2
+    calls = [small, large, small]
+    t = [[_dev(x) for x in (c.arena, c.part_off, c.part_len, c.begin)] for c in calls]
+    outs = [torch.zeros((c.begin.size - 1, 32), dtype=torch.uint8, device="cuda:0") for c in calls]
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    with Engine(1) as eng:
+        torch.cuda.synchronize()
+        for k, case in enumerate(calls):
+            _launch(eng, case, stream=streams[k % 2], tensors=t[k], out=outs[k])
+        torch.cuda.synchronize()
+        eng.device_status()
+        for k, case in enumerate(calls):
+            assert _bad_rows(outs[k].cpu().numpy(), M.expected_digests(case)) == [], k
+        ids, _ = _check_route(eng, small)                          # the last call's route: four slots, one lane
+        assert len(ids) == 4 and eng.parts_route_order().size == 1
+        assert eng.parts_route_stats()["calls"] == 3
+
+
+@gpu
 def test_capturable_into_a_graph(engine):
     """After one call of its size the routed call captures into a HIP graph; each replay
     hashes what the arena holds by then, long lists included."""

@@ -179,6 +179,19 @@ def test_check_route_rejects_wrong_routes():
     assert "the header says 5" in problems(long[1:], nbytes - 1008, sorted(short + long[:1], key=lambda l: -m.cls[l]))
 
 
+def test_workspace_layouts_and_growth_under_asan_ubsan(tmp_path):
+    """The planned and the routed workspace layout against their formulas written out, and
+    the grow / refuse decision of a device call's workspace (tests/cpp/call_workspace_check.cpp)."""
+    exe = tmp_path / "call_workspace_check"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wextra", "-Werror",
+                    "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "call_workspace_check.cpp")], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    # n x with_list x (the planned layout + m x flat_bytes routed ones); capacity x need x spare x capturing
+    assert "call_workspace ok: %d layouts, %d growth decisions" % (7 * 2 * (1 + 3 * 3), 4 * 4 * 3 * 2) in r.stdout
+
+
 def _room_ok(given, length, long_bytes):
     """parts_route.hpp room_ok restated in Python integers."""
     r = (length + 15) // 16 * 16
