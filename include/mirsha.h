@@ -969,6 +969,104 @@ int msha_dstreams_route_read(msha_dstreams* set, uint32_t* rows, uint64_t cap, u
                              uint64_t* routed_bytes);
 
 /*
+ * Device stream sets: jobs in call order with the long streams routed to the chain
+ * (ABI 10, additive: MSHA_HAS_STREAMS_DEVICE_JOBS_ROUTED tells a build that has it).
+ * NodeState.ActiveHash (pkg/testengine/recorder.go:288-359) is one stream a node, and
+ * Apply writes every committed request digest to its node's stream in commit order: a
+ * device-resident caller holds JOBS IN CALL ORDER whose few streams repeat and end up
+ * long. msha_dstreams_write_jobs_device takes that order and runs each stream as one
+ * lane; msha_dstreams_write_routed_device gives a long stream eight lanes and wants the
+ * CSR grouped by stream. This entry joins them inside one call: the jobs are grouped by
+ * stream on the GPU as in the first, and the grouped streams are written as in the
+ * second, the long ones on the eight-lane chain.
+ *
+ * SAME RESULT, SAME ERRORS as msha_dstreams_write_jobs_device over the same jobs,
+ * whatever `opts` holds: state, buffer and length of every stream are bit for bit that
+ * entry's. A stream may be named any number of times and its chunks append in job
+ * order; empty chunks contribute nothing; a job whose stream is >= n is DROPPED (no
+ * stream touched, its chunk not read, every other job exact) and msha_device_status()
+ * reports bit 32 once. The arena rules and the host checks (null pointers, d_arena's
+ * alignment, n_jobs >= 2^32 - 1) are that entry's; the bounds of `opts` are checked on
+ * the host as in msha_dstreams_write_routed_device. n_jobs == 0 returns MSHA_OK and
+ * launches nothing. Nothing here raises bit 4 or bit 16.
+ *
+ * WHAT IS ROUTED is the paragraph of msha_dstreams_write_routed_device with "row" read
+ * as "stream" and "its parts" as "its valid jobs". A stream is LONG when
+ *   floor((length[s] % 64 + the sum of its jobs' lengths) / 64) >= long_blocks;
+ * a dropped job's length counts for no stream. The caps never fail a call: a long
+ * stream that gets no slot or no room stays a lane and is as right as any; when every
+ * long stream fits both caps exactly the long streams are routed; of long streams of
+ * one total L exactly
+ * min(n_long, max_long, floor((long_bytes - MSHA_DEVICE_ARENA_SLACK) / round16(L))) are.
+ * DEFAULTS as there: long_blocks MSHA_DSTREAMS_ROUTE_LONG_BLOCKS_DEFAULT, max_long 16 x
+ * compute units, long_bytes 32 MiB.
+ *
+ * 3 * passes + 8 LAUNCHES (passes = ceil(bit_width(n) / 8)), all on `stream` (NULL: the
+ * context's own): the jobs entry's sort passes and its two CSR kernels, then the routed
+ * write's six in its order (init, measure, copy, chain, tail, write) over the grouped
+ * offsets, lengths and CSR, where row r is stream r and every stream is a row. No
+ * memset, no library stream, no host wait, and no kernel waits on another workgroup;
+ * the call captures into a HIP graph as a linear chain of kernel nodes, and a replay
+ * appends again. The six launches cover all n streams however few of them the jobs
+ * touch: O(n) lanes a call, most of which find no part.
+ *
+ * The workspace is this entry's own: the jobs entry's arrays, then the routed write's
+ * over n rows with its flatten buffer of long_bytes. A jobs call, a routed call and a
+ * call of this entry on one set share no memory. It belongs to the set and is freed in
+ * destroy; growth (a quarter of the arrays to spare, nothing for the buffer), the
+ * refusal on a capturing stream and the event that orders a call after the set's
+ * previous call of this entry are those of msha_dstreams_write_jobs_device.
+ *
+ * MEASURED (tools/dstream_bench.py jobs_long; profiles/streams_device/jobs_long.jsonl
+ * and README.md "Measurement 5"): see that file for what this entry gains on a few
+ * long streams and what it costs on many short ones. A caller that knows its streams
+ * are short calls msha_dstreams_write_jobs_device.
+ *
+ * MSHA_PARTS_TIMING and MSHA_PARTS_PLAN_WAVE_SUM apply as in the routed write.
+ */
+#define MSHA_HAS_STREAMS_DEVICE_JOBS_ROUTED 1
+int msha_dstreams_write_jobs_routed_device(msha_dstreams* set, const uint8_t* d_arena,
+                                           const uint32_t* d_job_stream, const uint64_t* d_job_off,
+                                           const uint64_t* d_job_len, uint64_t n_jobs,
+                                           const msha_route_opts* opts, void* stream);
+/* Counters of msha_dstreams_write_jobs_routed_device (msha_dstreams_stats,
+ * msha_dstreams_jobs_stats and msha_dstreams_route_stats count none of its calls; its
+ * chain launch counts in msha_stats as every chain launch does: launches_coop and
+ * launches_chain8). */
+typedef struct {
+  uint64_t calls;             /* calls that enqueued their launches */
+  uint64_t jobs;              /* jobs of those calls */
+  uint64_t launches_sort;     /* histogram, scan and scatter launches: 3 a pass */
+  uint64_t launches_rows;     /* the two CSR kernels */
+  uint64_t launches_route;    /* init and measure: 2 a call */
+  uint64_t launches_copy;     /* the flatten: one a call */
+  uint64_t launches_chain;    /* the eight-lane absorb chain: one a call */
+  uint64_t launches_tail;     /* the routed streams' tail rows and lengths: one a call */
+  uint64_t launches_write;    /* Write's row body over the streams that stayed lanes: one a call */
+  uint64_t last_passes;       /* radix passes of the last call: ceil(bit_width(n) / 8) */
+  uint64_t last_jobs;
+  uint64_t last_routed;       /* the last call's routed streams and ... */
+  uint64_t last_routed_bytes; /* ... the bytes of the flatten buffer they were given; both read back, and */
+  double last_kernel_ms;      /* the call's kernels timed by HIP events, only under MSHA_PARTS_TIMING=1
+                                 (read at each call; the call then waits for its kernels; never while
+                                 `stream` is being captured); otherwise these three are 0 */
+} msha_dstreams_jobs_route_stats;
+int msha_dstreams_get_jobs_route_stats(const msha_dstreams* set, msha_dstreams_jobs_route_stats* out);
+/* Diagnostic, synchronous (waits for the device), for the set's last call of this entry:
+ * the job order as msha_dstreams_jobs_read_order gives it (order[p] is the job applied
+ * p-th, argsort(min(stream, n), stable) exactly, up to order_cap entries; *n_jobs that
+ * call's job count, *n_valid how many leading positions are valid jobs), and the routed
+ * streams as msha_dstreams_route_read gives the routed rows (the stream ids, in no
+ * particular order, into streams[0 .. min(streams_cap, *n_routed)), their count into
+ * *n_routed, the bytes of the flatten buffer they were given into *routed_bytes). order
+ * and streams may be NULL when their cap is 0. Before any such call every count is 0.
+ * msha_dstreams_jobs_read_order and msha_dstreams_route_read keep meaning the last jobs
+ * call and the last routed call: this entry touches neither. */
+int msha_dstreams_jobs_route_read(msha_dstreams* set, uint32_t* order, uint64_t order_cap,
+                                  uint64_t* n_jobs, uint64_t* n_valid, uint32_t* streams,
+                                  uint64_t streams_cap, uint64_t* n_routed, uint64_t* routed_bytes);
+
+/*
  * Host-only helpers (no GPU needed).
  * msha_blocks_for_len: number of 64-byte compressions for an L-byte message,
  *   floor(L/64) + (L%64 < 56 ? 1 : 2)  (FIPS 180-4 5.1.1 padding).

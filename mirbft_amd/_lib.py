@@ -42,6 +42,7 @@ MSHA_HAS_STREAMS_DEVICE_JOBS = 1
 MSHA_HAS_ABSORB_CHAIN = 1
 MSHA_HAS_STREAMS_DEVICE_ROUTED = 1
 MSHA_DSTREAMS_ROUTE_LONG_BLOCKS_DEFAULT = 64
+MSHA_HAS_STREAMS_DEVICE_JOBS_ROUTED = 1
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -229,6 +230,25 @@ class MshaDstreamsRouteStats(ctypes.Structure):
     ]
 
 
+class MshaDstreamsJobsRouteStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", ctypes.c_uint64),
+        ("jobs", ctypes.c_uint64),
+        ("launches_sort", ctypes.c_uint64),
+        ("launches_rows", ctypes.c_uint64),
+        ("launches_route", ctypes.c_uint64),
+        ("launches_copy", ctypes.c_uint64),
+        ("launches_chain", ctypes.c_uint64),
+        ("launches_tail", ctypes.c_uint64),
+        ("launches_write", ctypes.c_uint64),
+        ("last_passes", ctypes.c_uint64),
+        ("last_jobs", ctypes.c_uint64),
+        ("last_routed", ctypes.c_uint64),
+        ("last_routed_bytes", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
 _setp = ctypes.c_void_p
 
 # name -> (restype, argtypes)
@@ -332,6 +352,12 @@ SIGNATURES = {
                                                          ctypes.POINTER(MshaRouteOpts), ctypes.c_void_p]),
     "msha_dstreams_get_route_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaDstreamsRouteStats)]),
     "msha_dstreams_route_read": (ctypes.c_int, [_setp, _u32p, ctypes.c_uint64, _u64p, _u64p]),
+    "msha_dstreams_write_jobs_routed_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                              ctypes.POINTER(MshaRouteOpts), ctypes.c_void_p]),
+    "msha_dstreams_get_jobs_route_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaDstreamsJobsRouteStats)]),
+    "msha_dstreams_jobs_route_read": (ctypes.c_int, [_setp, _u32p, ctypes.c_uint64, _u64p, _u64p, _u32p,
+                                                     ctypes.c_uint64, _u64p, _u64p]),
 }
 
 _lib = None
@@ -382,7 +408,7 @@ _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mi
               "parts_digest.hpp", "parts_plan.hpp", "parts_plan.hip", "parts_plan.cpp",
               "parts_route.hpp", "parts_route.cpp",
               "stream_device.hpp", "stream_device.hip", "stream_device.cpp", "stream_jobs.hpp", "stream_jobs.hip",
-              "stream_chain.hpp", "stream_chain.hip", "stream_write.hpp",
+              "stream_chain.hpp", "stream_chain.hip", "stream_write.hpp", "stream_jobs_route.hpp",
               "parts_concat.hpp", "parts_concat.hip", "parts_concat.cpp")
 
 

@@ -13,9 +13,13 @@
 // msha_dstreams_write_routed_device: the rows whose write compresses many blocks are
 // found on the GPU, flattened behind their stream's buffered bytes and absorbed by the
 // eight-lane chain, the others written as lanes (stream_chain.hip, kernels.hip
-// k_absorb_chain8; six launches). Each workspace is a CallWorkspace and follows the
-// workspace rule stated in call_workspace.hpp: it grows only outside stream capture, and
-// a call outside capture is ordered after the set's previous call of its kind.
+// k_absorb_chain8; six launches).
+// msha_dstreams_write_jobs_routed_device: the first one's grouping, then the second
+// one's six launches over the grouped CSR, which names every stream (no new kernel; the
+// workspace of both, stream_jobs_route.hpp). Each workspace is a CallWorkspace and
+// follows the workspace rule stated in call_workspace.hpp: it grows only outside stream
+// capture, and a call outside capture is ordered after the set's previous call of its
+// kind.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -28,6 +32,7 @@
 #include "stream_chain.hpp"
 #include "stream_device.hpp"
 #include "stream_jobs.hpp"
+#include "stream_jobs_route.hpp"
 #include "stream_state.hpp"
 
 // The workspace of the jobs calls and what msha_dstreams_jobs_read_order needs of the
@@ -48,6 +53,16 @@ struct DstreamRoute {
   msha_dstreams_route_stats st{};
 };
 
+// The workspace of the routed jobs calls (stream_jobs_route.hpp Layout), its own: a jobs
+// call, a routed call and a routed jobs call on one set share no memory. And what
+// msha_dstreams_jobs_route_read needs of the last one.
+struct DstreamJobsRoute {
+  msha::CallWorkspace ws;
+  uint64_t last_jobs = 0, last_slots = 0;
+  uint64_t at_pairs = 0, at_valid = 0, at_stream = 0, at_claim = 0;  // byte offsets in ws of the last call's arrays
+  msha_dstreams_jobs_route_stats st{};
+};
+
 struct msha_dstreams {
   msha_ctx* ctx = nullptr;
   msha::CtxDevice dev;
@@ -55,6 +70,7 @@ struct msha_dstreams {
   msha_dstreams_stats st{};
   DstreamJobs jobs;
   DstreamRoute route;
+  DstreamJobsRoute jobs_route;
 };
 
 namespace {
@@ -80,6 +96,7 @@ void release(msha_dstreams* s) {
   if (s->rows.length) (void)hipFree(s->rows.length);
   s->jobs.ws.release();
   s->route.ws.release();
+  s->jobs_route.ws.release();
 }
 
 // The row arguments every device call shares. Call with the lock held.
@@ -416,6 +433,167 @@ int msha_dstreams_route_read(msha_dstreams* s, uint32_t* rows, uint64_t cap, uin
       ++k;
     }
     *n_routed = k;
+    *routed_bytes = claim[msha::parts_route::kClaimBytes];
+  });
+}
+
+int msha_dstreams_write_jobs_routed_device(msha_dstreams* s, const uint8_t* d_arena, const uint32_t* d_job_stream,
+                                           const uint64_t* d_job_off, const uint64_t* d_job_len, uint64_t n_jobs,
+                                           const msha_route_opts* opts, void* stream) {
+  static const char* const kEntry = "msha_dstreams_write_jobs_routed_device";
+  namespace sj = msha::sjobs;
+  if (!s) return MSHA_ERR_INVALID_ARG;
+  if (n_jobs == 0) return MSHA_OK;
+  std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
+  if (!d_arena || !d_job_stream || !d_job_off || !d_job_len)
+    return msha::ctx_fail(s->ctx, MSHA_ERR_INVALID_ARG, "null pointer argument");
+  if (reinterpret_cast<uintptr_t>(d_arena) % MSHA_DEVICE_ALIGN)
+    return msha::bad_arg(s->ctx, kEntry, "d_arena must be 16-byte aligned");
+  if (n_jobs >= sj::kMaxJobs) return msha::bad_arg(s->ctx, kEntry, "n_jobs must be below 2^32 - 1");
+  // opts: the long_bytes bounds here, the max_long bound once the device is known
+  const int orc = msha::guard(s->ctx, [&] {
+    (void)msha::route_opts(kEntry, "stream", opts, 0, MSHA_DSTREAMS_ROUTE_LONG_BLOCKS_DEFAULT);
+  });
+  if (orc != MSHA_OK) return orc;
+
+  return msha::guard(s->ctx, [&] {
+    // a capturing stream allows no allocation: know that before the workspace would grow
+    const bool capturing = stream && msha::stream_capturing(static_cast<hipStream_t>(stream));
+    msha::CtxDevice d;  // the set's own (s->dev): the context's first device
+    const hipStream_t st = msha::device_entry(s->ctx, kEntry, stream, capturing, &d);
+
+    const msha_route_opts o = msha::route_opts(kEntry, "stream", opts, d.cus, MSHA_DSTREAMS_ROUTE_LONG_BLOCKS_DEFAULT);
+    const uint64_t n = s->rows.n;
+    DstreamJobsRoute& jr = s->jobs_route;
+    const msha::sjroute::Layout lay(n_jobs, n, o.max_long, o.long_bytes);
+    if (!lay.ok) throw msha::MshaError(MSHA_ERR_INVALID_ARG, std::string(kEntry) + ": the workspace size does not fit");
+    // the arrays grow with a quarter to spare, the flatten buffer is what was asked for
+    uint8_t* ws = jr.ws.acquire(kEntry, lay.bytes, lay.arrays / 4, capturing, st);
+
+    msha::StreamJobsArgs j;
+    j.job_stream = d_job_stream;
+    j.job_off = d_job_off;
+    j.job_len = d_job_len;
+    j.n_jobs = n_jobs;
+    j.n_streams = n;
+    j.pairs[0] = reinterpret_cast<uint2*>(ws + lay.jobs.pairs[0]);
+    j.pairs[1] = reinterpret_cast<uint2*>(ws + lay.jobs.pairs[1]);
+    j.goff = reinterpret_cast<uint64_t*>(ws + lay.jobs.off);
+    j.glen = reinterpret_cast<uint64_t*>(ws + lay.jobs.len);
+    j.counts = reinterpret_cast<uint32_t*>(ws + lay.jobs.counts);
+    j.begin = reinterpret_cast<uint64_t*>(ws + lay.jobs.begin);
+    j.err = s->dev.err;
+    j.passes = sj::pass_count(n);
+
+    // the routed write over the grouped CSR: row r is stream r, every stream a row, a
+    // stream without a valid job a row without parts; the dropped jobs lie behind begin[n]
+    msha::StreamRouteArgs a;
+    a.long_blocks = o.long_blocks;
+    a.max_long = o.max_long;
+    a.long_bytes = o.long_bytes;
+    a.rows = s->rows;
+    a.arena = d_arena;
+    a.part_off = j.goff;
+    a.part_len = j.glen;
+    a.begin = j.begin;
+    a.row = nullptr;
+    a.n_rows = n;
+    a.claim = reinterpret_cast<unsigned long long*>(ws + lay.claim);
+    a.taken = ws + lay.taken;
+    a.slot_row = reinterpret_cast<uint32_t*>(ws + lay.slot_row);
+    a.slot_stream = reinterpret_cast<uint32_t*>(ws + lay.slot_stream);
+    a.slot_t = reinterpret_cast<uint32_t*>(ws + lay.slot_t);
+    a.msg_off = reinterpret_cast<uint64_t*>(ws + lay.msg_off);
+    a.msg_len = reinterpret_cast<uint64_t*>(ws + lay.msg_len);
+    a.blocks = reinterpret_cast<uint64_t*>(ws + lay.blocks);
+    a.flat = ws + lay.flat;
+    a.err = s->dev.err;
+    a.wave_sum_parts = msha::wave_sum_parts();
+
+    // under MSHA_PARTS_TIMING=1 the claim counters are read back too, which makes the call wait
+    msha::LaunchTimer timer(st, !capturing && msha::LaunchTimer::wanted());
+    uint32_t sort_launches = 0, row_launches = 0;
+    msha::launch_check(msha::launch_stream_jobs(j, st, &sort_launches, &row_launches), "stream jobs launch");
+    msha::launch_check(msha::launch_sroute_init(a, st), "k_sroute_init launch");
+    msha::launch_check(msha::launch_sroute_measure(a, st), "k_sroute_measure launch");
+    msha::launch_check(msha::launch_sroute_copy(a, st), "k_sroute_copy launch");
+    msha::launch_check(msha::launch_absorb_chain8(s->rows.state, a.flat, a.msg_off, a.blocks, a.slot_stream,
+                                                  a.max_long, s->dev.err, st),
+                       "k_absorb_chain8 launch");
+    msha::ctx_count_launch(s->ctx, msha::kLaunchChain8);
+    msha::launch_check(msha::launch_sroute_tail(a, st), "k_sroute_tail launch");
+    msha::launch_check(msha::launch_dstream_write_rest(a, st), "k_dstream_write_rest launch");
+    jr.last_jobs = n_jobs;
+    jr.last_slots = a.max_long;
+    jr.at_pairs = lay.jobs.pairs[sj::sorted_buffer(j.passes)];
+    jr.at_valid = lay.jobs.begin + 8 * n;
+    jr.at_stream = lay.slot_stream;
+    jr.at_claim = lay.claim;
+    jr.ws.commit(st, capturing);
+
+    const float ms = timer.stop();
+    unsigned long long claim[msha::parts_route::kClaimWords] = {};
+    if (timer.enabled()) HIPCHK(hipMemcpy(claim, a.claim, sizeof claim, hipMemcpyDeviceToHost));
+    msha_dstreams_jobs_route_stats& c = jr.st;
+    c.calls++;
+    c.jobs += n_jobs;
+    c.launches_sort += sort_launches;
+    c.launches_rows += row_launches;
+    c.launches_route += 2;
+    c.launches_copy++;
+    c.launches_chain++;
+    c.launches_tail++;
+    c.launches_write++;
+    c.last_passes = j.passes;
+    c.last_jobs = n_jobs;
+    c.last_routed = claim[msha::parts_route::kClaimRouted];
+    c.last_routed_bytes = claim[msha::parts_route::kClaimBytes];
+    c.last_kernel_ms = ms;
+  });
+}
+
+int msha_dstreams_get_jobs_route_stats(const msha_dstreams* s, msha_dstreams_jobs_route_stats* out) {
+  if (!s || !out) return MSHA_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
+  *out = s->jobs_route.st;
+  return MSHA_OK;
+}
+
+int msha_dstreams_jobs_route_read(msha_dstreams* s, uint32_t* order, uint64_t order_cap, uint64_t* n_jobs,
+                                  uint64_t* n_valid, uint32_t* streams, uint64_t streams_cap, uint64_t* n_routed,
+                                  uint64_t* routed_bytes) {
+  if (!s || !n_jobs || !n_valid || !n_routed || !routed_bytes || (order_cap && !order) || (streams_cap && !streams))
+    return MSHA_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(msha::ctx_mutex(s->ctx));
+  *n_jobs = *n_valid = *n_routed = *routed_bytes = 0;
+  const DstreamJobsRoute& jr = s->jobs_route;
+  if (!jr.ws.ran()) return MSHA_OK;
+  return msha::guard(s->ctx, [&] {
+    HIPCHK(hipSetDevice(s->dev.id));
+    HIPCHK(hipDeviceSynchronize());
+    const uint8_t* ws = jr.ws.data();
+    uint64_t valid = 0;
+    HIPCHK(hipMemcpy(&valid, ws + jr.at_valid, 8, hipMemcpyDeviceToHost));
+    *n_jobs = jr.last_jobs;
+    *n_valid = valid < jr.last_jobs ? valid : jr.last_jobs;
+    const uint64_t k = jr.last_jobs < order_cap ? jr.last_jobs : order_cap;
+    if (k) {
+      std::vector<uint32_t> pairs(2 * k);  // (key, job index)
+      HIPCHK(hipMemcpy(pairs.data(), ws + jr.at_pairs, 8 * k, hipMemcpyDeviceToHost));
+      for (uint64_t p = 0; p < k; ++p) order[p] = pairs[2 * p + 1];
+    }
+    const uint64_t m = jr.last_slots;
+    std::vector<uint32_t> strm(m);
+    unsigned long long claim[msha::parts_route::kClaimWords] = {};
+    if (m) HIPCHK(hipMemcpy(strm.data(), ws + jr.at_stream, 4 * m, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(claim, ws + jr.at_claim, sizeof claim, hipMemcpyDeviceToHost));
+    uint64_t r = 0;
+    for (uint64_t i = 0; i < m; ++i) {
+      if (strm[i] == msha::schain::kNoStream) continue;  // a slot nobody filled
+      if (r < streams_cap) streams[r] = strm[i];
+      ++r;
+    }
+    *n_routed = r;
     *routed_bytes = claim[msha::parts_route::kClaimBytes];
   });
 }

@@ -12,7 +12,8 @@ device memory -- jobs in call order, a stream named any number of times -- group
 stream on the GPU inside the call: several launches, still on the caller's stream and
 capturable once its workspace exists. ``write_routed_device`` is ``write_device`` with the
 rows that compress many blocks found on the GPU and run on the eight-lane chain, eight
-lanes a stream instead of one. The device calls take torch tensors (``torch`` supplies
+lanes a stream instead of one; ``write_jobs_routed_device`` is the two in one call, jobs
+in call order whose long streams take the chain. The device calls take torch tensors (``torch`` supplies
 device memory and streams only); ``lengths``, ``export_state`` and ``import_state``
 are synchronous and use numpy, in the layout ``StreamSet`` exports.
 """
@@ -218,6 +219,61 @@ class DeviceStreamSet:
         self._check(self._lib.msha_dstreams_jobs_read_order(self._handle(), _p(order, ctypes.c_uint32), k,
                                                             ctypes.byref(n_jobs), ctypes.byref(n_valid)))
         return order[:n_jobs.value], n_valid.value
+
+    def write_jobs_routed_device(self, arena, job_stream, job_off, job_len, stream=None,
+                                 long_blocks: int = 0, max_long: int = 0, long_bytes: int = 0) -> None:
+        """write_jobs_device with its long streams on the eight-lane chain: the jobs are
+        grouped by stream on the GPU as there, then written as write_routed_device writes
+        the grouped CSR -- a stream whose valid jobs make its write compress long_blocks
+        64-byte blocks or more is flattened and absorbed with eight lanes, the others are
+        lanes. At most max_long streams and long_bytes bytes are routed; 0 takes a
+        default (64 blocks, 16 x compute units, 32 MiB). State, buffer, length, dropped
+        jobs and arena rules are write_jobs_device's whatever the three hold; 3 x passes +
+        8 launches, all on ``stream``."""
+        self._check_tensors(arena=arena, job_stream=job_stream, job_off=job_off, job_len=job_len)
+        n_jobs = job_stream.numel()
+        if job_off.numel() != n_jobs or job_len.numel() != n_jobs:
+            raise ValueError(f"job_stream has {n_jobs} entries, job_off {job_off.numel()}, job_len {job_len.numel()}")
+        if arena.data_ptr() % L.MSHA_DEVICE_ALIGN:
+            raise ValueError(f"arena must start on a {L.MSHA_DEVICE_ALIGN}-byte boundary")
+        for name, v, top in (("long_blocks", long_blocks, 1 << 32), ("max_long", max_long, 1 << 32),
+                             ("long_bytes", long_bytes, 1 << 64)):
+            if not 0 <= int(v) < top:
+                raise ValueError(f"{name} must be in [0, 2^{top.bit_length() - 1})")
+        if n_jobs == 0:
+            return
+        opts = L.MshaRouteOpts(int(long_blocks), int(max_long), int(long_bytes))
+        if arena.numel() == 0:          # nothing to read: an empty tensor has no address to pass
+            arena = job_off.new_zeros(2)
+        self._check(self._lib.msha_dstreams_write_jobs_routed_device(
+            self._handle(), arena.data_ptr(), job_stream.data_ptr(), job_off.data_ptr(), job_len.data_ptr(), n_jobs,
+            ctypes.byref(opts), Engine._stream_ptr(stream)))
+
+    def jobs_route_stats(self) -> dict:
+        """The counters of write_jobs_routed_device (stats(), jobs_stats() and route_stats()
+        count none of its calls); last_routed, last_routed_bytes and last_kernel_ms only
+        under MSHA_PARTS_TIMING=1."""
+        s = L.MshaDstreamsJobsRouteStats()
+        self._check(self._lib.msha_dstreams_get_jobs_route_stats(self._handle(), ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in L.MshaDstreamsJobsRouteStats._fields_}
+
+    def jobs_route_read(self):
+        """(order, n_valid, routed_streams, routed_bytes) of the last
+        write_jobs_routed_device (waits for the device): the job order and its count of
+        valid jobs as jobs_order() gives them, the streams it routed, in no particular
+        order, and the bytes of the flatten buffer they were given. A diagnostic;
+        jobs_order() and routed_rows() are not touched by that call."""
+        n_jobs, n_valid, n_routed, nbytes = (ctypes.c_uint64(0) for _ in range(4))
+        f = self._lib.msha_dstreams_jobs_route_read
+        self._check(f(self._handle(), None, 0, ctypes.byref(n_jobs), ctypes.byref(n_valid), None, 0,
+                      ctypes.byref(n_routed), ctypes.byref(nbytes)))
+        order = np.zeros(max(n_jobs.value, 1), dtype=np.uint32)
+        ids = np.zeros(max(n_routed.value, 1), dtype=np.uint32)
+        k, m = n_jobs.value, n_routed.value
+        if k or m:
+            self._check(f(self._handle(), _p(order, ctypes.c_uint32), k, ctypes.byref(n_jobs), ctypes.byref(n_valid),
+                          _p(ids, ctypes.c_uint32), m, ctypes.byref(n_routed), ctypes.byref(nbytes)))
+        return order[:k], n_valid.value, ids[:m], nbytes.value
 
     def _finish(self, fn, out, rows, stream) -> None:
         self._check_tensors(out=out, rows=rows)

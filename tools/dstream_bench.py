@@ -6,6 +6,7 @@ recorder's shape, and kernel against kernel over tools/parts_bench.py's part lis
     python3 tools/dstream_bench.py kernel   [--reps 7] [--out profiles/streams_device/kernel.jsonl]
     python3 tools/dstream_bench.py jobs     [--reps 7] [--out profiles/streams_device/jobs.jsonl]
     python3 tools/dstream_bench.py long     [--reps 7] [--out profiles/streams_device/long.jsonl]
+    python3 tools/dstream_bench.py jobs_long [--reps 7] [--out profiles/streams_device/jobs_long.jsonl]
 
 recorder  `--streams` (65,536) streams each appending `--digests` (20) 32-byte digests that
           sit in HBM as rows of a digest table (NodeState.Apply's shape, recorder.go:348).
@@ -43,6 +44,16 @@ long      write_routed_device against write_device, each a write + sum_device wi
           combined. Then the `long_blocks` sweep (8 .. 256) on 64 x 2,048 and on a mixed
           shape (65,536 x 20 with 32 streams of 2,048 among them). Every stream's digest of
           every route is checked against hashlib outside the timed window.
+jobs_long `long`'s four shapes given as jobs in commit-major order (job d * streams + s), the
+          call shape of NodeState.ActiveHash for a device-resident caller. Three arms, each a
+          reset, the write, sum_device and one synchronisation, timed by wall clock,
+          alternating in one process after a warm repetition of each:
+          (a) write_jobs_device: every stream a lane, however long;
+          (b) write_jobs_routed_device, all defaults;
+          (c) write_routed_device on the grouped CSR given: the floor that grouping cannot
+              beat.
+          A sample of every repetition's digests is checked against hashlib outside the
+          window. A difference is named only where it exceeds the two arms' spreads combined.
 Every figure is the median of `--reps` (>= 5) timed repetitions after warm ones, with
 (max - min) / median beside it. A sample of what was timed is checked against hashlib.
 A measurement, not a threshold. Needs the GPU; there is no fallback.
@@ -277,6 +288,72 @@ def long_rows(a, build):
         return lines
 
 
+def _jobs_long_shape(eng, n, k, reps, build, label):
+    import torch
+    from mirbft_amd import DeviceStreamSet
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(13)
+    table = torch.randint(0, 256, (n * k * 32 + 64,), dtype=torch.uint8, device=dev, generator=g)
+    # commit-major: job j = d * n + s is digest d of stream s, at table row j
+    job_stream = torch.arange(n, dtype=torch.int32, device=dev).repeat(k)
+    job_off = torch.arange(n * k, dtype=torch.int64, device=dev) * 32
+    job_len = torch.full((n * k,), 32, dtype=torch.int64, device=dev)
+    # (c)'s input, prepared outside the window: the same jobs grouped by stream
+    perm = torch.arange(n * k, dtype=torch.int64, device=dev).view(k, n).t().contiguous().view(-1)
+    g_off, g_len = job_off[perm].contiguous(), job_len[perm].contiguous()
+    begin = torch.arange(n + 1, dtype=torch.int64, device=dev) * k
+    out = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+    host = table.cpu().numpy()[: n * k * 32].reshape(k, n, 32)
+    check = sorted({0, 1, n // 2, n - 1})
+    want = {s: hashlib.sha256(host[:, s].tobytes()).digest() for s in check}
+    torch.cuda.synchronize()
+    with DeviceStreamSet(eng, n) as ds:
+        arms = (("jobs", lambda: ds.write_jobs_device(table, job_stream, job_off, job_len)),
+                ("jobs_routed", lambda: ds.write_jobs_routed_device(table, job_stream, job_off, job_len)),
+                ("routed_csr", lambda: ds.write_routed_device(table, g_off, g_len, begin)))
+        times = {name: [] for name, _ in arms}
+        for rep in range(reps + 1):                    # the first of each is the warm one
+            for name, arm in arms:
+                ds.reset_device()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                arm()
+                ds.sum_device(out)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                got = out.cpu().numpy()
+                for s_, w in want.items():
+                    assert got[s_].tobytes() == w, (label, name, rep, s_)
+                if rep:
+                    times[name].append((t1 - t0) * 1e3)
+        eng.device_status()
+        routed = int(ds.jobs_route_read()[2].size)
+        st = ds.jobs_route_stats()
+        launches = sum(v for f, v in st.items() if f.startswith("launches_")) // st["calls"]
+    a_, b_, c_ = (_stat(times[x]) for x in ("jobs", "jobs_routed", "routed_csr"))
+    spread = lambda s: s["max"] - s["min"]             # noqa: E731
+    gain, over = a_["median"] - b_["median"], b_["median"] - c_["median"]
+    return {"measure": "jobs_long", "shape": label, "streams": n, "digests_per_stream": k, "jobs": n * k,
+            "bytes": n * k * 32, "reps": reps, "routed_streams": routed, "passes": st["last_passes"],
+            "launches_per_jobs_routed_call": launches,
+            "write_jobs_ms": a_, "write_jobs_routed_ms": b_, "write_routed_csr_ms": c_,
+            "jobs_over_jobs_routed": round(a_["median"] / b_["median"], 3),
+            "jobs_minus_jobs_routed_ms": round(gain, 4), "spreads_jobs_jobs_routed_ms": round(spread(a_) + spread(b_), 4),
+            "jobs_routed_faster_than_jobs_by_more_than_the_spreads": bool(gain > spread(a_) + spread(b_)),
+            "jobs_routed_slower_than_jobs_by_more_than_the_spreads": bool(-gain > spread(a_) + spread(b_)),
+            "jobs_routed_minus_csr_ms": round(over, 4), "spreads_jobs_routed_csr_ms": round(spread(b_) + spread(c_), 4),
+            "jobs_routed_above_the_floor_by_more_than_the_spreads": bool(over > spread(b_) + spread(c_)),
+            "build": build["id"]}
+
+
+def jobs_long(a, build):
+    from mirbft_amd import Engine
+    with Engine(1) as eng:
+        return [_jobs_long_shape(eng, n, k, a.reps, build, label)
+                for label, n, k in (("a", 4, 8192), ("b", 64, 2048), ("c", 256, 512), ("d", 1 << 16, 20))]
+
+
 def _blocks(length):
     length = length.astype(np.uint64)
     return (length >> np.uint64(6)) + np.where((length & np.uint64(63)) < 56, 1, 2).astype(np.uint64)
@@ -360,7 +437,7 @@ def kernel(a, build):
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("measure", choices=["recorder", "kernel", "jobs", "long"])
+    ap.add_argument("measure", choices=["recorder", "kernel", "jobs", "long", "jobs_long"])
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--streams", type=int, default=1 << 16)
     ap.add_argument("--digests", type=int, default=20)
@@ -378,7 +455,7 @@ def main() -> int:
         ap.error("%s measures enqueue-only calls: unset MSHA_PARTS_TIMING" % a.measure)
     from mirbft_amd import _lib
     build = _lib.require_tree_build("dstream_bench")
-    lines = {"recorder": recorder, "kernel": kernel, "jobs": jobs, "long": long_rows}[a.measure](a, build)
+    lines = {"recorder": recorder, "kernel": kernel, "jobs": jobs, "long": long_rows, "jobs_long": jobs_long}[a.measure](a, build)
     for ln in lines:
         print(json.dumps(ln))
     if a.out:
