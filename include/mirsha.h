@@ -1067,6 +1067,86 @@ int msha_dstreams_jobs_route_read(msha_dstreams* set, uint32_t* order, uint64_t 
                                   uint64_t streams_cap, uint64_t* n_routed, uint64_t* routed_bytes);
 
 /*
+ * Digests verified on the GPU (ABI 10, additive: MSHA_HAS_VERIFY_DEVICE tells a build
+ * that has it). What the state machine does with almost every digest it gets back is
+ * compare it with one it already holds: applyVerifyBatchHashResult compares a forwarded
+ * batch's digest with VerifyBatch.ExpectedDigest (pkg/statemachine/batch_tracker.go:167-195),
+ * a request's digest is compared with the digests other nodes acknowledged
+ * (pkg/processor/clients.go:152-177), an EpochChange's with its acks
+ * (epoch_target.go:486-528). This entry does that comparison where the device entries
+ * above left the digests, so that a caller brings down 40 bytes (how many differ, which
+ * is the first) and a short list instead of 32 bytes a digest. Measured times, against
+ * the download and against the same expression in torch: profiles/verify/README.md.
+ *
+ * MATCH. Slot i, for i in [0, n), matches iff all 32 bytes of d_got[32 i ..] equal
+ * d_expected[32 e ..], e = d_expected_idx ? d_expected_idx[i] : i. d_expected holds
+ * n_expected rows; with d_expected_idx NULL slot i expects row i and n_expected must
+ * equal n. An index may repeat (N nodes' acks of one request expect one row). An index
+ * e >= n_expected is a mismatch: it counts in bad and in bad_index, and no byte of
+ * d_expected is read for that slot. No bit of the device error word is used and
+ * msha_device_status() is untouched by this entry: d_result carries everything.
+ *
+ * MASK. Bit i % 64 of d_bad_mask[i / 64] is 1 iff slot i differs. Every one of the
+ * ceil(n / 64) words is written, and the bits at and past n in the last word are 0: the
+ * caller never clears the mask.
+ *
+ * LIST. d_bad_list[0 .. listed) holds the first listed = min(bad, list_cap) differing
+ * slots in ascending order. Entries at and past listed are not written. d_bad_list may
+ * be NULL when list_cap is 0.
+ *
+ * RESULT. *d_result (device memory) is written whole by every call that launches.
+ *
+ * READ AND WRITE CONTRACT. Read: the 32 n bytes of d_got; of d_expected only rows that
+ * some slot's index names, all below n_expected; the n entries of d_expected_idx (the
+ * entries of differing slots twice). Written: the ceil(n / 64) mask words, the first
+ * listed entries of d_bad_list, *d_result. Nothing else. d_bad_mask and d_result are
+ * 8-byte aligned and d_bad_list and d_expected_idx 4-byte aligned, as their types say;
+ * the outputs must not overlap the inputs.
+ *
+ * Checked on the host (MSHA_ERR_INVALID_ARG, each with a text): null pointers; d_got or
+ * d_expected not MSHA_DEVICE_ALIGN-aligned; n at or above 2^32 - 1; n != n_expected
+ * without d_expected_idx; list_cap > 0 with d_bad_list NULL. n == 0 returns MSHA_OK and
+ * launches nothing (*d_result is left as it was).
+ *
+ * ONE STREAM, capturable: two kernels (compare, scan) go on `stream` (NULL: the
+ * context's own). There is no memset, no library stream, no host wait and no workspace
+ * of the context's, and no workgroup waits on another, so the call captures into a HIP
+ * graph as two kernel nodes and a replay verifies what the arrays hold by then. The scan
+ * is one workgroup, serial in chunks of msha_verify_stats.scan_words mask words; its
+ * share of the call is in profiles/verify/README.md. The one allocation is the context's
+ * error word on its first device call: on a capturing stream a context that has made no
+ * device call yet fails with MSHA_ERR_INVALID_ARG and says to make one call of this size
+ * outside the capture first.
+ */
+#define MSHA_HAS_VERIFY_DEVICE 1
+typedef struct {
+  uint64_t n;          /* digests compared */
+  uint64_t bad;        /* slots that differ (out-of-range expected indices included) */
+  uint64_t first_bad;  /* the smallest differing slot; n when bad == 0 */
+  uint64_t listed;     /* min(bad, list_cap): entries written to d_bad_list */
+  uint64_t bad_index;  /* of bad, slots whose d_expected_idx entry was >= n_expected */
+} msha_verify_result;  /* device memory, written whole by every call */
+int msha_verify_digests_device(msha_ctx* ctx,
+                               const uint8_t* d_got, uint64_t n,
+                               const uint8_t* d_expected, uint64_t n_expected,
+                               const uint32_t* d_expected_idx,
+                               uint64_t* d_bad_mask,
+                               uint32_t* d_bad_list, uint64_t list_cap,
+                               msha_verify_result* d_result, void* stream);
+/* Counters of msha_verify_digests_device (msha_stats, msha_parts_stats and
+ * msha_concat_stats are untouched by it). */
+typedef struct {
+  uint64_t calls;         /* calls that enqueued their launches */
+  uint64_t digests;       /* slots they compared (n) */
+  uint64_t launches;      /* kernel launches: two a call */
+  uint64_t scan_words;    /* mask words the scan takes a chunk: a constant, valid from context creation */
+  double last_kernel_ms;  /* the last call's kernels timed by HIP events, only under MSHA_PARTS_TIMING=1
+                             (read at each call; the call then waits for its kernels; never while
+                             `stream` is being captured); otherwise 0 */
+} msha_verify_stats;
+int msha_get_verify_stats(const msha_ctx* ctx, msha_verify_stats* out);
+
+/*
  * Host-only helpers (no GPU needed).
  * msha_blocks_for_len: number of 64-byte compressions for an L-byte message,
  *   floor(L/64) + (L%64 < 56 ? 1 : 2)  (FIPS 180-4 5.1.1 padding).

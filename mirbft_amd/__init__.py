@@ -7,7 +7,8 @@ reference's ``processor.Hasher`` / ``ProcessHashActions`` surface.
 from .engine import Engine, MshaError, blocks_for_len, device_count, pack_parts, partition_by_blocks
 from .processor import (Action, ActionHashRequest, ActionList, EventHashResult, EventList, GPUHasher,
                         HashOrigin, HashOriginBatch, HashOriginEpochChange, HashOriginVerifyBatch,
-                        ProcessHashActions, ProcessorError, action_hash, checkpoint_hashes)
+                        ProcessHashActions, ProcessorError, action_hash, checkpoint_hashes,
+                        verify_batches_device)
 from .streams import StreamSet
 from .streams_device import DeviceStreamSet
 
@@ -16,5 +17,6 @@ __all__ = [
     "Action", "ActionHashRequest", "ActionList", "EventHashResult", "EventList", "GPUHasher",
     "HashOrigin", "HashOriginBatch", "HashOriginEpochChange", "HashOriginVerifyBatch",
     "ProcessHashActions", "ProcessorError", "action_hash", "checkpoint_hashes",
+    "verify_batches_device",
     "StreamSet", "DeviceStreamSet",
 ]

@@ -35,6 +35,7 @@ MSHA_STREAM_STATE_BYTES = 108
 MSHA_PARTS_FOLD = 1
 MSHA_HAS_PARTS_CONCAT = 1
 MSHA_HAS_PARTS_ROUTED = 1
+MSHA_HAS_VERIFY_DEVICE = 1
 MSHA_ROUTE_LONG_BLOCKS_DEFAULT = 64
 MSHA_ROUTE_LONG_BYTES_DEFAULT = 32 << 20
 MSHA_HAS_STREAMS_DEVICE = 1
@@ -159,6 +160,26 @@ class MshaConcatStats(ctypes.Structure):
         ("lists", ctypes.c_uint64),
         ("launches", ctypes.c_uint64),
         ("last_bytes", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
+class MshaVerifyResult(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("bad", ctypes.c_uint64),
+        ("first_bad", ctypes.c_uint64),
+        ("listed", ctypes.c_uint64),
+        ("bad_index", ctypes.c_uint64),
+    ]
+
+
+class MshaVerifyStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", ctypes.c_uint64),
+        ("digests", ctypes.c_uint64),
+        ("launches", ctypes.c_uint64),
+        ("scan_words", ctypes.c_uint64),
         ("last_kernel_ms", ctypes.c_double),
     ]
 
@@ -322,6 +343,11 @@ SIGNATURES = {
                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "msha_get_concat_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaConcatStats)]),
+    "msha_verify_digests_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                  ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                  ctypes.c_void_p]),
+    "msha_get_verify_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaVerifyStats)]),
     "msha_hash_actions_device_routed": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                                        ctypes.c_uint64, ctypes.POINTER(MshaRouteOpts),
@@ -409,6 +435,7 @@ _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mi
               "parts_route.hpp", "parts_route.cpp",
               "stream_device.hpp", "stream_device.hip", "stream_device.cpp", "stream_jobs.hpp", "stream_jobs.hip",
               "stream_chain.hpp", "stream_chain.hip", "stream_write.hpp", "stream_jobs_route.hpp",
+              "verify.hpp", "verify.hip", "verify.cpp",
               "parts_concat.hpp", "parts_concat.hip", "parts_concat.cpp")
 
 

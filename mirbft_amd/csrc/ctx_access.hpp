@@ -2,7 +2,7 @@
 // defined there): its lock, its first device, its error text and what the device
 // entries keep in it (the states by name only: call_workspace.hpp defines them). Defined
 // at the end of mirsha.cpp; used, through host_call.hpp, by streams.cpp, parts.cpp,
-// parts_plan.cpp, parts_concat.cpp, parts_route.cpp and stream_device.cpp.
+// parts_plan.cpp, parts_concat.cpp, parts_route.cpp, stream_device.cpp and verify.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,6 +33,8 @@ int ctx_fail(msha_ctx* ctx, int code, const char* msg);
 msha_parts_stats& ctx_parts_stats(msha_ctx* ctx);
 // The counters of msha_concat_lists_device (parts_concat.cpp). Call with the lock held.
 msha_concat_stats& ctx_concat_stats(msha_ctx* ctx);
+// The counters of msha_verify_digests_device (verify.cpp). Call with the lock held.
+msha_verify_stats& ctx_verify_stats(msha_ctx* ctx);
 
 // What msha_hash_actions_device_planned and _routed keep in the context. Call with the lock held.
 struct PartsPlanState;

@@ -486,6 +486,28 @@ hipError_t launch_concat_measure(const ConcatArgs& a, hipStream_t st);
 hipError_t launch_concat_scan(const ConcatArgs& a, hipStream_t st);
 hipError_t launch_concat_copy(const ConcatArgs& a, hipStream_t st);
 
+// Digests verified against expected ones (verify.hip, msha_verify_digests_device): slot i
+// of got against row expected_idx[i] (null: row i) of expected, 32 bytes a row. The
+// compare writes the mask, bit i % 64 of word i / 64 set where slot i differs, all
+// ceil(n / 64) words; the scan, one workgroup, writes the first min(bad, list_cap)
+// differing slots to bad_list in ascending order and the five words of result. Layout and
+// walk: verify.hpp. Two kernels on one stream, no workspace, no device error bit and no
+// host wait: capturable.
+struct VerifyArgs {
+  const uint8_t* got = nullptr;
+  uint64_t n = 0;
+  const uint8_t* expected = nullptr;
+  uint64_t n_expected = 0;
+  const uint32_t* expected_idx = nullptr;  // n, or null
+  uint64_t* bad_mask = nullptr;            // ceil(n / 64)
+  uint32_t* bad_list = nullptr;            // list_cap, null when that is 0
+  uint64_t list_cap = 0;
+  uint64_t* result = nullptr;              // msha_verify_result as five words
+};
+// k_verify_compare, then k_verify_scan; one launch each.
+hipError_t launch_verify_compare(const VerifyArgs& a, hipStream_t st);
+hipError_t launch_verify_scan(const VerifyArgs& a, hipStream_t st);
+
 // Clock probe (msha_clock_probe): `workgroups` x 256 lanes compress `blocks`
 // register-resident blocks each; stamps gets (memtime, memrealtime) at start and
 // end per workgroup, 4 words each.

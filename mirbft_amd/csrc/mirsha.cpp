@@ -532,6 +532,7 @@ struct msha_ctx {
   msha_parts_stats parts_stats{};  // msha_hash_actions_device (msha_get_parts_stats)
   msha::PartsPlanState parts_plan;  // msha_hash_actions_device_planned (parts_plan.cpp)
   msha_concat_stats concat_stats{};  // msha_concat_lists_device (parts_concat.cpp)
+  msha_verify_stats verify_stats{};  // msha_verify_digests_device (verify.cpp)
   msha::PartsRouteState parts_route;  // msha_hash_actions_device_routed (parts_route.cpp)
   // allocations handed out by msha_pinned_alloc: (pointer, mapped bytes), 0 =
   // hipHostMalloc, else an mmap striped over NUMA nodes and hipHostRegister'ed
@@ -3303,6 +3304,8 @@ int ctx_fail(msha_ctx* ctx, int code, const char* msg) { return fail(ctx, code, 
 msha_parts_stats& ctx_parts_stats(msha_ctx* ctx) { return ctx->parts_stats; }
 
 msha_concat_stats& ctx_concat_stats(msha_ctx* ctx) { return ctx->concat_stats; }
+
+msha_verify_stats& ctx_verify_stats(msha_ctx* ctx) { return ctx->verify_stats; }
 
 PartsPlanState& ctx_parts_plan(msha_ctx* ctx) { return ctx->parts_plan; }
 

@@ -243,7 +243,8 @@ class Engine:
             dev = self._dev_index = self._device_index()
         sizes = {"off": 8, "length": 8, "begin": 8, "order": 4, "idx": 4, "arena": 1, "table": 1,
                  "nblocks": 8, "prefix": 8, "state": 4, "part_off": 8, "part_len": 8, "list_begin": 8,
-                 "action_list": 4, "dst": 1, "msg_off": 8, "msg_len": 8, "select": 4}
+                 "action_list": 4, "dst": 1, "msg_off": 8, "msg_len": 8, "select": 4,
+                 "got": 1, "expected": 1, "expected_idx": 4, "mask": 8, "bad_list": 4, "result": 8}
         for name, t in list(tensors.items()) + [("out", out)]:
             if t is None:
                 continue
@@ -519,6 +520,51 @@ class Engine:
         s = L.MshaConcatStats()
         self._check(self._lib.msha_get_concat_stats(self._ctx, ctypes.byref(s)))
         return {name: getattr(s, name) for name, _ in L.MshaConcatStats._fields_}
+
+    def verify_digests_device(self, got, expected, mask, result, expected_idx=None, bad_list=None,
+                              stream=None) -> None:
+        """msha_verify_digests_device: slot i of got (32 n bytes) is compared with row
+        expected_idx[i] of expected (expected_idx None: row i, as many rows as slots). Bit
+        i % 64 of mask[i // 64] is set where slot i differs, every one of the ceil(n / 64)
+        words written; bad_list (may be None) receives the first min(bad, its length)
+        differing slots in ascending order; result, five 8-byte words, receives n, bad,
+        first_bad (n when none differs), listed and bad_index (slots whose index was out
+        of range: they differ, and nothing of expected is read for them). Enqueue-only:
+        nothing is read back here, and device_status() has nothing to report."""
+        self._check_device_args(0, None, got=got, expected=expected, expected_idx=expected_idx, mask=mask,
+                                bad_list=bad_list, result=result)
+        if got.numel() % 32 or expected.numel() % 32:
+            raise ValueError(f"got and expected hold 32-byte rows (got {got.numel()} and {expected.numel()} bytes)")
+        n, n_expected = got.numel() // 32, expected.numel() // 32
+        if expected_idx is None and n_expected != n:
+            raise ValueError(f"without expected_idx expected must have as many rows as got ({n_expected} != {n})")
+        if expected_idx is not None and expected_idx.numel() != n:
+            raise ValueError(f"expected_idx has {expected_idx.numel()} entries, expected {n}")
+        if mask.numel() < (n + 63) // 64:
+            raise ValueError(f"mask holds {mask.numel()} words, needs {(n + 63) // 64}")
+        if result.numel() != 5:
+            raise ValueError(f"result must hold 5 words (got {result.numel()})")
+        if got.data_ptr() % L.MSHA_DEVICE_ALIGN:
+            raise ValueError(f"got must start on a {L.MSHA_DEVICE_ALIGN}-byte boundary")
+        if expected.data_ptr() % L.MSHA_DEVICE_ALIGN:
+            raise ValueError(f"expected must start on a {L.MSHA_DEVICE_ALIGN}-byte boundary")
+        if n == 0:
+            return
+        if n_expected == 0:             # every index is out of range; still a valid address
+            expected = got
+        list_cap = 0 if bad_list is None else bad_list.numel()
+        self._check(self._lib.msha_verify_digests_device(
+            self._ctx, got.data_ptr(), n, expected.data_ptr(), n_expected,
+            None if expected_idx is None else expected_idx.data_ptr(), mask.data_ptr(),
+            bad_list.data_ptr() if list_cap else None, list_cap, result.data_ptr(), self._stream_ptr(stream)))
+
+    def verify_stats(self) -> dict:
+        """msha_get_verify_stats: calls, digests and launches of verify_digests_device,
+        scan_words (mask words the scan takes a chunk: a constant) and, under
+        MSHA_PARTS_TIMING=1, the last call's kernel time."""
+        s = L.MshaVerifyStats()
+        self._check(self._lib.msha_get_verify_stats(self._ctx, ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in L.MshaVerifyStats._fields_}
 
     def clock_probe(self, blocks_per_lane: int = 48) -> dict:
         """msha_clock_probe: the clock the first GPU holds under the hash

@@ -300,6 +300,48 @@ def checkpoint_hashes(hasher: GPUHasher, intervals: Sequence[tuple]) -> List[byt
     return [bytes(r) for r in out]
 
 
+def verify_batches_device(hasher: GPUHasher, table, idx, begin, expected, list_cap: int = 64, stream=None):
+    """VerifyBatch in HBM (applyVerifyBatchHashResult, batch_tracker.go:175-195): batch i
+    is the request digests table[idx[begin[i] : begin[i + 1]]], its digest (what
+    digest_of_digests_device gives) is compared on the GPU with expected[32 i ..], and
+    only the answer comes down. All four are torch tensors on the engine's GPU, laid out
+    as Engine.digest_of_digests_device and Engine.verify_digests_device take them.
+    Returns (bad, first_bad, bad_indices): how many batches differ, the first of them
+    (the batch count when none does) and the first min(bad, list_cap) of them in
+    ascending order. One 40-byte read, and, only when bad > 0, one read of the listed
+    indices. stream: a torch.cuda.Stream of the caller's (None: the engine's own)."""
+    import torch
+    eng = hasher.engine
+    n = begin.numel() - 1
+    if n < 0:
+        raise ProcessorError("verify_batches_device: begin must have at least one entry")
+    if n == 0:
+        return 0, 0, []
+    dev = begin.device
+    digests = torch.empty(32 * n, dtype=torch.uint8, device=dev)
+    mask = torch.empty((n + 63) // 64, dtype=torch.int64, device=dev)
+    result = torch.empty(5, dtype=torch.int64, device=dev)
+    bad_list = torch.empty(int(list_cap), dtype=torch.int32, device=dev) if list_cap > 0 else None
+    # The two calls go on `stream`; None, or torch's default stream, means the engine's own
+    # stream, which is no stream of torch's: then the whole device is waited for, before
+    # (what torch still owes the inputs) and after. A stream of the caller's is waited
+    # for alone.
+    own = not eng._stream_ptr(stream)
+    if own:
+        torch.cuda.synchronize(dev)
+    eng.digest_of_digests_device(table, idx, begin, digests, stream=stream)
+    eng.verify_digests_device(digests, expected, mask, result, bad_list=bad_list, stream=stream)
+    if own or not hasattr(stream, "synchronize"):
+        torch.cuda.synchronize(dev)
+    else:
+        stream.synchronize()
+    _, bad, first_bad, listed, _ = (int(x) for x in result.cpu().tolist())
+    indices = []
+    if bad > 0 and listed > 0:
+        indices = [int(x) & 0xFFFFFFFF for x in bad_list[:listed].cpu().tolist()]
+    return bad, first_bad, indices
+
+
 def _epoch_change_aliases(reqs: Sequence[ActionHashRequest]) -> List[int]:
     """alias[i] = an earlier request carrying request i's EpochChange payload,
     else -1 (the Go drop-in's epochChangeAliases, gpuhash.go). Each origin's
