@@ -1147,6 +1147,110 @@ typedef struct {
 int msha_get_verify_stats(const msha_ctx* ctx, msha_verify_stats* out);
 
 /*
+ * Digests grouped by value on the GPU (ABI 10, additive: MSHA_HAS_GROUP_DEVICE tells a
+ * build that has it). Beside comparing a digest with one it holds (the entry above), the
+ * state machine uses almost every digest it receives as a MAP KEY: a sequence tallies how
+ * many nodes sent the same digest (pkg/statemachine/sequence.go:73-74, 271-277, 331-340:
+ * prepares and commits are map[string]int, agreements := s.prepares[string(s.digest)]),
+ * a checkpoint's quorum is values map[string][]nodeID (checkpoints.go:264-290), the
+ * request acks are keyed by string(ack.Digest) per (client, reqNo)
+ * (client_hash_disseminator.go:346-349, 415-504), and so are batchesByDigest
+ * (batch_tracker.go:20, 85-91) and parsedByDigest (epoch_change.go:23, 42-50). This entry
+ * is that map for digests that lie in device memory: which of them are equal, how many of
+ * each, and which value has the most, left in HBM in order of first occurrence. Its
+ * d_group_first and d_group also are the table of distinct digests and the index into it
+ * that msha_digest_of_digests_device and msha_verify_digests_device take. Measured times,
+ * against the download with a host map and against a sort of the rows in torch, and where
+ * it loses: profiles/group/README.md.
+ *
+ * KEY. Slot i's key, for i in [0, n), is (d_scope ? d_scope[i] : 0, the 32 bytes at
+ * d_digests + 32 i). Two slots are in one group iff their keys are equal in all 36 bytes.
+ * Equality is always that full compare: a hash or a tag that matches never joins two
+ * slots by itself (a wrong join is a wrong quorum). d_scope is what lets one call serve
+ * many maps: the sequence number, the checkpoint, the (client, reqNo) index.
+ *
+ * FIRST. d_first[i] is the smallest slot with slot i's key: the group's leader, <= i.
+ *
+ * GROUP. Groups are numbered 0 .. groups - 1 in ascending order of their leader, that is
+ * in order of first occurrence. d_group[i] is the number of slot i's group, and
+ * d_members[i] (d_members may be NULL) the number of slots in it.
+ *
+ * LIST. For g < listed = min(groups, group_cap), d_group_first[g] is group g's leader and
+ * d_group_count[g] its member count. Entries at and past listed are not written. Both may
+ * be NULL when group_cap is 0.
+ *
+ * RESULT. *d_result (device memory) is written whole by every call that launches.
+ *
+ * CANONICAL. Every output is a function of the inputs alone. The groups are found with an
+ * open-addressing table of capacity bit_ceil(2 n) (at least 64) and a keyed hash, but no
+ * output depends on the table's size, the hash, its seed or the order in which workgroups
+ * ran: the same inputs give the same bytes in every call. The seed is 64 bits the context
+ * draws when it is created (the digests come off the wire: with a fixed function a
+ * sender could aim every key at one probe chain), and it changes time only.
+ *
+ * READ AND WRITE CONTRACT. Read: the 32 n bytes of d_digests, as whole 16-byte pieces (a
+ * row may be read several times), and the n entries of d_scope. Written: d_first, d_group
+ * and d_members, n entries each, the first listed entries of d_group_first and
+ * d_group_count, and *d_result. Nothing else of the caller's is touched. d_first is
+ * written by one kernel and read by later ones. d_result is 8-byte aligned and the
+ * 32-bit arrays 4-byte aligned, as their types say; the outputs must not overlap the
+ * inputs or one another.
+ *
+ * Checked on the host (MSHA_ERR_INVALID_ARG, each with a text): null pointers; d_digests
+ * not MSHA_DEVICE_ALIGN-aligned; n above 2^30 (the table has at most 2^31 positions and a
+ * position is a uint32_t); group_cap > 0 with d_group_first or d_group_count NULL. n == 0
+ * returns MSHA_OK and launches nothing (*d_result is left as it was). No bit of the
+ * device error word is used and msha_device_status() is untouched by this entry.
+ *
+ * ONE STREAM, capturable: six kernels (init, insert, resolve, scan, rank, fill: group.hip)
+ * go on `stream` (NULL: the context's own), counted in msha_group_stats.launches. There is
+ * no memset, no library stream and no host wait, every dependency is a kernel boundary and
+ * no workgroup waits on another, so the call captures into a HIP graph as a chain of six
+ * kernel nodes, and a replay groups what the arrays hold by then.
+ *
+ * WORKSPACE. The table, where each slot's probe stopped, the leaders' counts and ids and
+ * the tile totals are a workspace of this entry's own in the context: 4 bytes a table
+ * position (8 to 16 a slot), 12 bytes a slot and 4 a 256 slots, 20 to 28 bytes a slot in
+ * all. It follows the rule of the other device calls' workspaces: it grows only outside
+ * stream capture and never shrinks, a call outside capture is ordered after the previous
+ * group call, whatever stream that was on, by an event, and on a capturing stream a call
+ * that would have to allocate (the workspace, or a fresh context's error word) fails with
+ * MSHA_ERR_INVALID_ARG and says to make one call of this size outside the capture first.
+ * msha_ctx_destroy releases it.
+ *
+ * Two diagnostics, read at each call: MSHA_GROUP_SEED replaces the context's seed, and
+ * MSHA_GROUP_FORCE_HOME=h gives every key the home position h mod capacity, so that a
+ * test reaches the probe chain and its wrap-around at small shapes. Neither changes an
+ * output byte.
+ */
+#define MSHA_HAS_GROUP_DEVICE 1
+typedef struct {
+  uint64_t n;          /* slots grouped */
+  uint64_t groups;     /* distinct (scope, digest) keys */
+  uint64_t listed;     /* min(groups, group_cap): entries written to d_group_first / d_group_count */
+  uint64_t max_count;  /* members of the largest group */
+  uint64_t max_group;  /* the smallest group id that has max_count members */
+} msha_group_result;   /* device memory, written whole by every call that launches */
+int msha_group_digests_device(msha_ctx* ctx,
+                              const uint8_t* d_digests, uint64_t n,
+                              const uint32_t* d_scope,        /* may be NULL */
+                              uint32_t* d_first, uint32_t* d_group,
+                              uint32_t* d_members,            /* may be NULL */
+                              uint32_t* d_group_first, uint32_t* d_group_count, uint64_t group_cap,
+                              msha_group_result* d_result, void* stream);
+/* Counters of msha_group_digests_device (no other entry's counters move with it). */
+typedef struct {
+  uint64_t calls;         /* calls that enqueued their launches */
+  uint64_t digests;       /* slots they grouped (n) */
+  uint64_t launches;      /* kernel launches: six a call */
+  uint64_t table_slots;   /* table positions of the last call: bit_ceil(2 n), at least 64 */
+  double last_kernel_ms;  /* the last call's kernels timed by HIP events, only under MSHA_PARTS_TIMING=1
+                             (read at each call; the call then waits for its kernels; never while
+                             `stream` is being captured); otherwise 0 */
+} msha_group_stats;
+int msha_get_group_stats(const msha_ctx* ctx, msha_group_stats* out);
+
+/*
  * Host-only helpers (no GPU needed).
  * msha_blocks_for_len: number of 64-byte compressions for an L-byte message,
  *   floor(L/64) + (L%64 < 56 ? 1 : 2)  (FIPS 180-4 5.1.1 padding).

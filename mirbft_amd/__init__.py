@@ -8,7 +8,7 @@ from .engine import Engine, MshaError, blocks_for_len, device_count, pack_parts,
 from .processor import (Action, ActionHashRequest, ActionList, EventHashResult, EventList, GPUHasher,
                         HashOrigin, HashOriginBatch, HashOriginEpochChange, HashOriginVerifyBatch,
                         ProcessHashActions, ProcessorError, action_hash, checkpoint_hashes,
-                        verify_batches_device)
+                        dedupe_digests_device, tally_digests_device, verify_batches_device)
 from .streams import StreamSet
 from .streams_device import DeviceStreamSet
 
@@ -17,6 +17,6 @@ __all__ = [
     "Action", "ActionHashRequest", "ActionList", "EventHashResult", "EventList", "GPUHasher",
     "HashOrigin", "HashOriginBatch", "HashOriginEpochChange", "HashOriginVerifyBatch",
     "ProcessHashActions", "ProcessorError", "action_hash", "checkpoint_hashes",
-    "verify_batches_device",
+    "verify_batches_device", "tally_digests_device", "dedupe_digests_device",
     "StreamSet", "DeviceStreamSet",
 ]

@@ -36,6 +36,7 @@ MSHA_PARTS_FOLD = 1
 MSHA_HAS_PARTS_CONCAT = 1
 MSHA_HAS_PARTS_ROUTED = 1
 MSHA_HAS_VERIFY_DEVICE = 1
+MSHA_HAS_GROUP_DEVICE = 1
 MSHA_ROUTE_LONG_BLOCKS_DEFAULT = 64
 MSHA_ROUTE_LONG_BYTES_DEFAULT = 32 << 20
 MSHA_HAS_STREAMS_DEVICE = 1
@@ -180,6 +181,26 @@ class MshaVerifyStats(ctypes.Structure):
         ("digests", ctypes.c_uint64),
         ("launches", ctypes.c_uint64),
         ("scan_words", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
+class MshaGroupResult(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("groups", ctypes.c_uint64),
+        ("listed", ctypes.c_uint64),
+        ("max_count", ctypes.c_uint64),
+        ("max_group", ctypes.c_uint64),
+    ]
+
+
+class MshaGroupStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", ctypes.c_uint64),
+        ("digests", ctypes.c_uint64),
+        ("launches", ctypes.c_uint64),
+        ("table_slots", ctypes.c_uint64),
         ("last_kernel_ms", ctypes.c_double),
     ]
 
@@ -348,6 +369,11 @@ SIGNATURES = {
                                                   ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                                   ctypes.c_void_p]),
     "msha_get_verify_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaVerifyStats)]),
+    "msha_group_digests_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    "msha_get_group_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaGroupStats)]),
     "msha_hash_actions_device_routed": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                                        ctypes.c_uint64, ctypes.POINTER(MshaRouteOpts),
@@ -436,6 +462,7 @@ _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mi
               "stream_device.hpp", "stream_device.hip", "stream_device.cpp", "stream_jobs.hpp", "stream_jobs.hip",
               "stream_chain.hpp", "stream_chain.hip", "stream_write.hpp", "stream_jobs_route.hpp",
               "verify.hpp", "verify.hip", "verify.cpp",
+              "group.hpp", "group.hip", "group.cpp",
               "parts_concat.hpp", "parts_concat.hip", "parts_concat.cpp")
 
 

@@ -1,5 +1,6 @@
 // What the device entries of several launches share (msha_hash_actions_device_planned and
-// _routed, msha_dstreams_write_jobs_device and _write_routed_device): the workspace each
+// _routed, msha_dstreams_write_jobs_device and _write_routed_device,
+// msha_group_digests_device): the workspace each
 // of them owns, what the two parts entries keep in the context, and the arguments they
 // read alike. Host-only.
 //
@@ -10,6 +11,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
+#include <random>
 #include <string>
 
 #include "host_call.hpp"
@@ -90,6 +93,24 @@ struct PartsRouteState {
   uint64_t last_lists = 0, last_slots = 0;  // n_lists and max_long of the last call
   uint64_t at_order = 0, at_chain = 0, at_out_idx = 0, at_claim = 0;  // byte offsets in ws of its arrays
   msha_parts_route_stats stats{};
+};
+
+// What msha_group_digests_device (group.cpp) keeps in the context: a workspace of its own
+// (the table, the positions, the counts, the ids and the tile totals: group.hpp Layout),
+// the seed of its hash, drawn when the context is created, and its counters.
+// msha_ctx_destroy releases ws.
+inline uint64_t draw_seed() {
+  try {
+    std::random_device rd;
+    return (uint64_t)rd() << 32 ^ (uint64_t)rd();
+  } catch (...) {  // no entropy source: the clock still differs from run to run
+    return (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count() * 0x9E3779B97F4A7C15ull;
+  }
+}
+struct GroupState {
+  CallWorkspace ws;
+  uint64_t seed = draw_seed();
+  msha_group_stats stats{};
 };
 
 // MSHA_PARTS_PLAN_WAVE_SUM (A/B runs, read at each call), or parts_plan::kWaveSumParts.

@@ -2,7 +2,8 @@
 // defined there): its lock, its first device, its error text and what the device
 // entries keep in it (the states by name only: call_workspace.hpp defines them). Defined
 // at the end of mirsha.cpp; used, through host_call.hpp, by streams.cpp, parts.cpp,
-// parts_plan.cpp, parts_concat.cpp, parts_route.cpp, stream_device.cpp and verify.cpp.
+// parts_plan.cpp, parts_concat.cpp, parts_route.cpp, stream_device.cpp, verify.cpp and
+// group.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,6 +42,11 @@ struct PartsPlanState;
 struct PartsRouteState;
 PartsPlanState& ctx_parts_plan(msha_ctx* ctx);
 PartsRouteState& ctx_parts_route(msha_ctx* ctx);
+// What msha_group_digests_device keeps in the context (group.cpp): workspace, seed and
+// counters. Call with the lock held.
+struct GroupState;
+GroupState& ctx_group_state(msha_ctx* ctx);
+msha_group_stats& ctx_group_stats(msha_ctx* ctx);
 // Counts a launch_digest_batch launch of a device entry in msha_stats (the routed
 // entry's chain: launches_coop and launches_chain8), as mirsha.cpp's own device entries
 // count theirs. kind: the kernels.hpp LaunchKind the launcher reported.

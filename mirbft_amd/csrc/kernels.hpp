@@ -508,6 +508,42 @@ struct VerifyArgs {
 hipError_t launch_verify_compare(const VerifyArgs& a, hipStream_t st);
 hipError_t launch_verify_scan(const VerifyArgs& a, hipStream_t st);
 
+// Digests grouped by value (group.hip, msha_group_digests_device): slot i's key is
+// (scope[i] or 0, the 32 bytes of row i); first[i] the smallest slot with slot i's key,
+// group[i] the group's number in order of first occurrence, members[i] its size, the
+// first min(groups, group_cap) groups' leaders and sizes in group_first / group_count and
+// the five words of result. The table, the positions, the counts, the ids and the tile
+// totals are the workspace's (group.hpp Layout). Six kernels on one stream, every
+// dependency a kernel boundary, no device error bit and no host wait: capturable.
+struct GroupArgs {
+  const uint8_t* digests = nullptr;
+  uint64_t n = 0;
+  const uint32_t* scope = nullptr;    // n, or null: every scope 0
+  uint32_t* first = nullptr;          // n
+  uint32_t* group = nullptr;          // n
+  uint32_t* members = nullptr;        // n, or null
+  uint32_t* group_first = nullptr;    // group_cap, null when that is 0
+  uint32_t* group_count = nullptr;    // group_cap, null when that is 0
+  uint64_t group_cap = 0;
+  uint64_t* result = nullptr;         // msha_group_result as five words
+  uint64_t* head = nullptr;           // the workspace: group.hpp Layout
+  uint32_t* table = nullptr;
+  uint32_t* pos = nullptr;
+  uint32_t* count = nullptr;
+  uint32_t* id = nullptr;
+  uint32_t* totals = nullptr;
+  uint64_t capacity = 0;              // table positions: group::capacity(n)
+  uint64_t seed = 0;                  // of the hash
+  uint32_t force_home = 0, force_at = 0;  // MSHA_GROUP_FORCE_HOME: every key's home is force_at
+};
+// k_group_init, _insert, _resolve, _scan, _rank, _fill, in this order; one launch each.
+hipError_t launch_group_init(const GroupArgs& a, hipStream_t st);
+hipError_t launch_group_insert(const GroupArgs& a, hipStream_t st);
+hipError_t launch_group_resolve(const GroupArgs& a, hipStream_t st);
+hipError_t launch_group_scan(const GroupArgs& a, hipStream_t st);
+hipError_t launch_group_rank(const GroupArgs& a, hipStream_t st);
+hipError_t launch_group_fill(const GroupArgs& a, hipStream_t st);
+
 // Clock probe (msha_clock_probe): `workgroups` x 256 lanes compress `blocks`
 // register-resident blocks each; stamps gets (memtime, memrealtime) at start and
 // end per workgroup, 4 words each.

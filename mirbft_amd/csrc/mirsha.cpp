@@ -534,6 +534,7 @@ struct msha_ctx {
   msha_concat_stats concat_stats{};  // msha_concat_lists_device (parts_concat.cpp)
   msha_verify_stats verify_stats{};  // msha_verify_digests_device (verify.cpp)
   msha::PartsRouteState parts_route;  // msha_hash_actions_device_routed (parts_route.cpp)
+  msha::GroupState group;  // msha_group_digests_device (group.cpp)
   // allocations handed out by msha_pinned_alloc: (pointer, mapped bytes), 0 =
   // hipHostMalloc, else an mmap striped over NUMA nodes and hipHostRegister'ed
   std::vector<std::pair<void*, uint64_t>> pinned;
@@ -2596,6 +2597,7 @@ void msha_ctx_destroy(msha_ctx* ctx) {
     if (&d == &ctx->devs[0]) {  // their workspaces live on the first device
       ctx->parts_plan.ws.release();
       ctx->parts_route.ws.release();
+      ctx->group.ws.release();
     }
     d.release();
   }
@@ -3310,6 +3312,10 @@ msha_verify_stats& ctx_verify_stats(msha_ctx* ctx) { return ctx->verify_stats; }
 PartsPlanState& ctx_parts_plan(msha_ctx* ctx) { return ctx->parts_plan; }
 
 PartsRouteState& ctx_parts_route(msha_ctx* ctx) { return ctx->parts_route; }
+
+GroupState& ctx_group_state(msha_ctx* ctx) { return ctx->group; }
+
+msha_group_stats& ctx_group_stats(msha_ctx* ctx) { return ctx->group.stats; }
 
 void ctx_count_launch(msha_ctx* ctx, int kind) { count_launch(ctx, nullptr, static_cast<LaunchKind>(kind)); }
 

@@ -244,7 +244,9 @@ class Engine:
         sizes = {"off": 8, "length": 8, "begin": 8, "order": 4, "idx": 4, "arena": 1, "table": 1,
                  "nblocks": 8, "prefix": 8, "state": 4, "part_off": 8, "part_len": 8, "list_begin": 8,
                  "action_list": 4, "dst": 1, "msg_off": 8, "msg_len": 8, "select": 4,
-                 "got": 1, "expected": 1, "expected_idx": 4, "mask": 8, "bad_list": 4, "result": 8}
+                 "got": 1, "expected": 1, "expected_idx": 4, "mask": 8, "bad_list": 4, "result": 8,
+                 "digests": 1, "scope": 4, "first": 4, "group": 4, "members": 4, "group_first": 4,
+                 "group_count": 4}
         for name, t in list(tensors.items()) + [("out", out)]:
             if t is None:
                 continue
@@ -565,6 +567,50 @@ class Engine:
         s = L.MshaVerifyStats()
         self._check(self._lib.msha_get_verify_stats(self._ctx, ctypes.byref(s)))
         return {name: getattr(s, name) for name, _ in L.MshaVerifyStats._fields_}
+
+    def group_digests_device(self, digests, first, group, result, scope=None, members=None, group_first=None,
+                             group_count=None, stream=None) -> None:
+        """msha_group_digests_device: slot i's key is (scope[i], or 0 with scope None, and
+        the 32 bytes digests[32 i ..]); slots with equal keys are one group. first[i]
+        receives the smallest slot with slot i's key, group[i] the group's number (groups
+        are numbered in order of first occurrence), members[i] (may be None) its size;
+        group_first and group_count (both or neither; as long as each other) the leader
+        and the size of the first min(groups, their length) groups; result, five 8-byte
+        words, n, groups, listed, max_count and max_group (the smallest group id of that
+        size). Enqueue-only: nothing is read back here, and device_status() has nothing
+        to report."""
+        self._check_device_args(0, None, digests=digests, scope=scope, first=first, group=group, members=members,
+                                group_first=group_first, group_count=group_count, result=result)
+        if digests.numel() % 32:
+            raise ValueError(f"digests holds 32-byte rows (got {digests.numel()} bytes)")
+        n = digests.numel() // 32
+        for name, t in (("scope", scope), ("first", first), ("group", group), ("members", members)):
+            if t is not None and t.numel() != n:
+                raise ValueError(f"{name} has {t.numel()} entries, expected {n}")
+        if (group_first is None) != (group_count is None):
+            raise ValueError("group_first and group_count go together: both or neither")
+        group_cap = 0 if group_first is None else group_first.numel()
+        if group_cap and group_count.numel() != group_cap:
+            raise ValueError(f"group_count has {group_count.numel()} entries, group_first {group_cap}")
+        if result.numel() != 5:
+            raise ValueError(f"result must hold 5 words (got {result.numel()})")
+        if digests.data_ptr() % L.MSHA_DEVICE_ALIGN:
+            raise ValueError(f"digests must start on a {L.MSHA_DEVICE_ALIGN}-byte boundary")
+        if n == 0:
+            return
+        self._check(self._lib.msha_group_digests_device(
+            self._ctx, digests.data_ptr(), n, None if scope is None else scope.data_ptr(), first.data_ptr(),
+            group.data_ptr(), None if members is None else members.data_ptr(),
+            group_first.data_ptr() if group_cap else None, group_count.data_ptr() if group_cap else None, group_cap,
+            result.data_ptr(), self._stream_ptr(stream)))
+
+    def group_stats(self) -> dict:
+        """msha_get_group_stats: calls, digests and launches (six a call) of
+        group_digests_device, the last call's table positions and, under
+        MSHA_PARTS_TIMING=1, its kernel time."""
+        s = L.MshaGroupStats()
+        self._check(self._lib.msha_get_group_stats(self._ctx, ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in L.MshaGroupStats._fields_}
 
     def clock_probe(self, blocks_per_lane: int = 48) -> dict:
         """msha_clock_probe: the clock the first GPU holds under the hash

@@ -342,6 +342,58 @@ def verify_batches_device(hasher: GPUHasher, table, idx, begin, expected, list_c
     return bad, first_bad, indices
 
 
+def tally_digests_device(hasher: GPUHasher, digests, scope=None, group_cap: int = 64, stream=None):
+    """The digest-keyed maps of the state machine in HBM (prepares and commits,
+    sequence.go:73-74, 271-277; a checkpoint's values, checkpoints.go:264-290; the acks
+    per (client, reqNo), client_hash_disseminator.go:415-504): slot i's key is
+    (scope[i], the 32 bytes digests[32 i ..]), scope None meaning one map. digests is a
+    uint8 tensor of 32 n bytes and scope an int32 tensor of n entries, both on the
+    engine's GPU. Returns (groups, max_count, max_group, first, group, members,
+    group_first, group_count): how many distinct keys there are, the size of the largest
+    group and its number, and the tensors Engine.group_digests_device fills, the last two
+    cut to min(groups, group_cap) entries. One 40-byte read. stream: a torch.cuda.Stream
+    of the caller's (None: the engine's own)."""
+    import torch
+    eng = hasher.engine
+    n = digests.numel() // 32
+    dev = digests.device
+    first, group, members = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    cap = int(group_cap)
+    group_first = torch.empty(cap, dtype=torch.int32, device=dev) if cap > 0 else None
+    group_count = torch.empty(cap, dtype=torch.int32, device=dev) if cap > 0 else None
+    empty = torch.empty(0, dtype=torch.int32, device=dev)
+    if n == 0:
+        return 0, 0, 0, first, group, members, empty, empty
+    result = torch.empty(5, dtype=torch.int64, device=dev)
+    # stream handling as in verify_batches_device: None, or torch's default stream, means
+    # the engine's own stream, and then the whole device is waited for, before and after
+    own = not eng._stream_ptr(stream)
+    if own:
+        torch.cuda.synchronize(dev)
+    eng.group_digests_device(digests, first, group, result, scope=scope, members=members, group_first=group_first,
+                             group_count=group_count, stream=stream)
+    if own or not hasattr(stream, "synchronize"):
+        torch.cuda.synchronize(dev)
+    else:
+        stream.synchronize()
+    _, groups, listed, max_count, max_group = (int(x) for x in result.cpu().tolist())
+    return (groups, max_count, max_group, first, group, members,
+            group_first[:listed] if cap > 0 else empty, group_count[:listed] if cap > 0 else empty)
+
+
+def dedupe_digests_device(hasher: GPUHasher, digests, stream=None):
+    """(table, idx): the distinct digests among the 32 n bytes of `digests`, in order of
+    first occurrence, as a [groups, 32] uint8 tensor, and int32 idx with
+    table[idx[i]] == digest i -- what Engine.digest_of_digests_device and
+    Engine.verify_digests_device(expected_idx=...) take. Everything stays on the GPU; the
+    one read is tally_digests_device's 40 bytes (the table's length)."""
+    n = digests.numel() // 32
+    groups, _, _, _, idx, _, group_first, _ = tally_digests_device(hasher, digests, group_cap=max(n, 1),
+                                                                   stream=stream)
+    table = digests.view(-1, 32)[group_first[:groups].long()]
+    return table, idx
+
+
 def _epoch_change_aliases(reqs: Sequence[ActionHashRequest]) -> List[int]:
     """alias[i] = an earlier request carrying request i's EpochChange payload,
     else -1 (the Go drop-in's epochChangeAliases, gpuhash.go). Each origin's
