@@ -452,8 +452,11 @@ def lib() -> ctypes.CDLL:
 
 
 # The files msha_build_id()'s src hash covers, in the Makefile's order (SRCS).
-_SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip", "mirsha.cpp",
+_SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip",
               os.path.join("..", "..", "include", "mirsha.h"),
+              "msha_error.hpp", "host_plan.hpp", "ctx.hpp", "ctx.cpp", "host_small.hpp", "host_small.cpp",
+              "host_pipeline.hpp", "host_pipeline.cpp", "host_direct.hpp", "host_direct.cpp",
+              "host_entries.cpp", "device_batch.cpp",
               "stream_kernels.hip", "stream_pack.hpp", "ctx_access.hpp", "host_call.hpp", "workspace_rule.hpp",
               "call_workspace.hpp", "stream_state.hpp", "streams.cpp",
               "parts_gather.hpp", "parts_kernels.hip", "parts.cpp",

@@ -1,9 +1,9 @@
-// What a translation unit outside mirsha.cpp may reach of a context (msha_ctx is
-// defined there): its lock, its first device, its error text and what the device
+// What a translation unit that does not include ctx.hpp may reach of a context (msha_ctx
+// is defined there): its lock, its first device, its error text and what the device
 // entries keep in it (the states by name only: call_workspace.hpp defines them). Defined
-// at the end of mirsha.cpp; used, through host_call.hpp, by streams.cpp, parts.cpp,
+// at the end of ctx.cpp; used, through host_call.hpp, by streams.cpp, parts.cpp,
 // parts_plan.cpp, parts_concat.cpp, parts_route.cpp, stream_device.cpp, verify.cpp and
-// group.cpp.
+// group.cpp. The host paths and device_batch.cpp include ctx.hpp and see the context itself.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,7 +48,7 @@ struct GroupState;
 GroupState& ctx_group_state(msha_ctx* ctx);
 msha_group_stats& ctx_group_stats(msha_ctx* ctx);
 // Counts a launch_digest_batch launch of a device entry in msha_stats (the routed
-// entry's chain: launches_coop and launches_chain8), as mirsha.cpp's own device entries
+// entry's chain: launches_coop and launches_chain8), as device_batch.cpp's entries
 // count theirs. kind: the kernels.hpp LaunchKind the launcher reported.
 void ctx_count_launch(msha_ctx* ctx, int kind);
 // Has a device call already allocated the first device's error word? Until then

@@ -17,13 +17,9 @@
 #include "../../include/mirsha.h"
 #include "ctx_access.hpp"
 #include "kernels.hpp"
+#include "msha_error.hpp"
 
 namespace msha {
-
-struct MshaError : std::runtime_error {
-  int code;
-  MshaError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
 
 // The error of a failed HIP call: what names the call (or the kernel launched).
 inline MshaError hip_fail(const char* what, hipError_t e) {

@@ -2,42 +2,19 @@
 // on the CPU (no GPU, no kernels): the alias detection, the size-class order,
 // the batch scan and block partition, and the direct path's granule marking and
 // upload enumeration are the intricate, index-heavy parts of the host pipeline
-// (mirbft_amd/csrc/mirsha.cpp; the direct path's lane planning runs on the GPU,
-// plan.hip, and is covered by the -m gpu tests). This
-// file includes mirsha.cpp itself so its internal functions are reachable, stubs
-// the kernel launchers (never called here), and checks every result against a
+// (mirbft_amd/csrc/host_plan.hpp; the direct path's lane planning runs on the GPU,
+// plan.hip, and is covered by the -m gpu tests). host_plan.hpp is HIP-free, so this
+// file includes it as the library's units do, and checks every result against a
 // plain reference computed in this file, over random and edge-case inputs.
-// Built by tests/cpp/Makefile (target asan) with g++ -fsanitize=address,undefined;
+// Built by tests/cpp/Makefile (targets asan, tsan) with plain g++ -fsanitize=...;
 // run by tests/test_host_sanitize.py.
-#include "../../mirbft_amd/csrc/mirsha.cpp"
+#include "../../mirbft_amd/csrc/host_plan.hpp"
 
 #include <cstdio>
 #include <map>
 #include <random>
 
-namespace msha {
-// Kernel launchers are GPU code (kernels.hip); the host planning never launches.
-bool plan_split(uint64_t, int, int, SplitPlan*, int) { return false; }
-hipError_t launch_digest_batch(const uint8_t*, const uint64_t*, const uint64_t*, const uint32_t*,
-                               const uint32_t*, uint64_t, uint8_t*, uint32_t*, int, int, hipStream_t,
-                               const SplitPlan*, LaunchKind*, const LaneGate*) {
-  abort();
-}
-hipError_t launch_digest_uniform(const uint8_t*, uint64_t, uint64_t, uint64_t, uint8_t*, uint32_t*, int,
-                                 hipStream_t, LaunchKind*) {
-  abort();
-}
-hipError_t launch_digest_of_digests(const uint8_t*, const uint32_t*, const uint64_t*, uint64_t, uint8_t*,
-                                    uint32_t*, hipStream_t, const SplitPlan*, LaunchKind*) {
-  abort();
-}
-hipError_t launch_plan(const PlanArgs&, hipStream_t) { abort(); }
-hipError_t launch_fold_plan(const FoldArgs&, hipStream_t, hipStream_t, hipEvent_t, hipEvent_t) { abort(); }
-hipError_t launch_fold_longs(const FoldArgs&, int, hipStream_t) { abort(); }
-hipError_t launch_fold_fill(const FoldArgs&, uint8_t*, hipStream_t) { abort(); }
-hipError_t launch_clock_probe(uint32_t, uint32_t, uint64_t*, uint32_t*, hipStream_t) { abort(); }
-bool uses_coop(uint64_t, int, int) { abort(); }
-}  // namespace msha
+using namespace msha;
 
 static int failures = 0;
 #define CHECK(c, ...)                                     \
@@ -326,20 +303,21 @@ static void direct_upload_cases(std::mt19937_64& rng) {
 }
 
 // A context over several physical GPUs runs its whole-batch phases on a pool of
-// its full host-thread share (guarded() installs it for the call, then restores
-// the caller's pool); alias detection on it matches the reference.
+// its full host-thread share (guarded() installs it for the call through PoolScope,
+// then restores the caller's pool); alias detection on it matches the reference.
 static void wide_pool_case(std::mt19937_64& rng) {
   setenv("MSHA_HOST_THREADS", "12", 1);
   {
-    msha_ctx ctx;
-    ctx.devs.resize(2);
-    ctx.devs[0].id = 0;
-    ctx.devs[1].id = 1;  // two physical GPUs: host_threads_total = 12 (the override), at most the machine's
+    std::unique_ptr<WorkerPool> wide;  // the context's
+    // two physical GPUs: host_threads_total = 12 (the override), at most the machine's
     const unsigned want = std::min(12u, std::max(1u, std::thread::hardware_concurrency()));
     unsigned seen = 0;
-    const int rc = guarded(&ctx, [&] { seen = plan_threads(1u << 20); });
-    CHECK(rc == MSHA_OK && (seen == want || (want <= 16 && seen == WorkerPool::get().size())),
-          "wide pool: %u threads, want %u (rc %d)", seen, want, rc);
+    {
+      PoolScope scope(wide, 2);
+      seen = plan_threads(1u << 20);
+    }
+    CHECK(seen == want || (want <= 16 && seen == WorkerPool::get().size()), "wide pool: %u threads, want %u", seen,
+          want);
     CHECK(tl_pool == nullptr, "wide pool: caller's pool not restored");
     const uint64_t n = (1u << 20) + 3;
     std::vector<uint64_t> off(n), len(n);
@@ -347,7 +325,10 @@ static void wide_pool_case(std::mt19937_64& rng) {
       len[i] = rng() % 300;
       off[i] = rng() % 16 == 0 ? (rng() % 64) * 512 : (1u << 20) + 512 * i;
     }
-    guarded(&ctx, [&] { check_alias("wide pool", off, len); });
+    {
+      PoolScope scope(wide, 2);
+      check_alias("wide pool", off, len);
+    }
   }
   unsetenv("MSHA_HOST_THREADS");
 }

@@ -55,13 +55,14 @@ KIND_NAMES = ("uniform-even", "uniform-odd", "near-uniform (lane 0 odd)", "near-
 MAX_SEGMENTS_DOD = 12           # kernels.hpp:63 kMaxSegmentsDod
 IDX_STAGE = 1536                # kernels.hip:700 DigestSrc::kIdxStage
 PER_LANE = IDX_STAGE // WAVE    # kernels.hip:715 kPer: 24 staged indices a lane
-SMALL_MSGS = 65536              # mirsha.cpp:1058 small_msgs()
-SMALL_DOD_BYTES = 1 << 20       # mirsha.cpp:1061 kSmallDodBytes
-SMALL_BYTES = 4 << 20           # mirsha.cpp:1057 small_bytes(), MSHA_SMALL_BYTES
+SMALL_MSGS = 65536              # host_plan.hpp small_msgs()
+SMALL_DOD_BYTES = 1 << 20       # host_plan.hpp kSmallDodBytes
+SMALL_BYTES = 4 << 20           # host_plan.hpp small_bytes(), MSHA_SMALL_BYTES
 
 
 def plan_split(n, c, policy="auto"):
-    """kernels.hip:1770 plan_split() with cap kMaxSegmentsDod (mirsha.cpp:2923, 3154):
+    """kernels.hip:1770 plan_split() with cap kMaxSegmentsDod (the split_for calls of
+    host_entries.cpp msha_digest_of_digests and device_batch.cpp msha_digest_of_digests_device):
     None, or n_main, chains, segments and groups."""
     sp = KM.plan_split(n, c, policy)
     if sp is None:
@@ -77,13 +78,13 @@ def is_staged(span, act):
 
 
 def host_small(n, n_idx, small_bytes=SMALL_BYTES):
-    """mirsha.cpp:2877 (small_call, :1062): the host entry packs the rows and hashes
+    """host_entries.cpp msha_digest_of_digests (host_plan.hpp small_call): the host entry packs the rows and hashes
     them as plain messages."""
     return small_bytes > 0 and n <= SMALL_MSGS and 32 * n_idx <= small_bytes and 32 * n_idx <= SMALL_DOD_BYTES
 
 
 def chain_blocks(cnt):
-    """kernels.hip:749: nb = cnt / 2 + 1 (also blocks_for(32 cnt), mirsha.cpp:72)."""
+    """kernels.hip:749: nb = cnt / 2 + 1 (also host_plan.hpp blocks_for(32 cnt))."""
     return np.asarray(cnt, dtype=np.int64) // 2 + 1
 
 
@@ -93,7 +94,7 @@ def segment_bounds(nb, seg, segments):
 
 
 def shard_bounds(counts, k):
-    """mirsha.cpp:459-488 partition(): bounds[s] = the first message whose block
+    """host_plan.hpp partition(): bounds[s] = the first message whose block
     range's midpoint reaches s / k of all blocks."""
     b = chain_blocks(counts)
     n = len(b)

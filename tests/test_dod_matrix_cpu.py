@@ -22,7 +22,7 @@ EDGE_WHO = ("spread", "first", "middle", "last")
 
 def test_restated_rules():
     """kernels.hip:1770-1785 (plan_split with the cap of 12), :716 (the stage) and
-    mirsha.cpp:2877 (the small path), at their edges."""
+    host_entries.cpp msha_digest_of_digests (the small path), at their edges."""
     for c in CUS:
         S = 4 * c
         assert DM.plan_split(64 * S, c) is None and DM.plan_split(64 * (S - 1), c) is None
@@ -47,7 +47,7 @@ def test_restated_rules():
 
 
 def test_shard_bounds_follow_the_block_midpoints():
-    """mirsha.cpp:459-488 by its definition, brute force."""
+    """host_plan.hpp partition() by its definition, brute force."""
     rng = np.random.default_rng(5)
     for _ in range(20):
         cnt = rng.integers(0, 40, int(rng.integers(1, 60)))
@@ -398,7 +398,7 @@ def _model_launch(b, rows, m, sp, fault):
 
 
 def model(t, pattern, index_pattern, c, fault=None):
-    """The block streams of a case's messages (mirsha.cpp:2888-2931: every shard gets
+    """The block streams of a case's messages (host_entries.cpp msha_digest_of_digests: every shard gets
     idx + i0 and begin - i0)."""
     begin = DM.case_begin(t, pattern, c).astype(np.int64)
     table, idx = DM.build_index(index_pattern, int(begin[-1]), KM._salt(t["name"], pattern, index_pattern))

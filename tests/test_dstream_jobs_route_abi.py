@@ -41,7 +41,12 @@ def test_symbols_declared_bound_and_exported():
 def test_the_new_header_is_in_both_build_lists():
     text = open(os.path.join(ROOT, "mirbft_amd", "csrc", "Makefile")).read()
     assert "stream_jobs_route.hpp" in L._SRC_FILES and "stream_jobs_route.hpp" in text.split("SRC_ID")[0]
-    assert "stream_jobs_route.hpp" in text.split("$(BUILD)/stream_device.o:")[1].split("$(HIPCC)")[0]
+    # stream_device.o is rebuilt when the header changes: the compiler lists each object's
+    # headers beside it (-MMD), the Makefile includes those lists, and the one the build
+    # left for stream_device.o names the header
+    assert "-MMD" in text.split("$(BUILD)/%.o: %.cpp")[1].split("\n\n")[0]
+    assert "-include $(wildcard $(BUILD)/*.d)" in text
+    assert "stream_jobs_route.hpp" in open(os.path.join(ROOT, "mirbft_amd", "csrc", "stream_device.d")).read()
     assert os.path.exists(os.path.join(ROOT, "mirbft_amd", "csrc", "stream_jobs_route.hpp"))
     # the Makefile's order is the binding's: the build id is a hash over the files in it
     srcs = text.split("SRCS :=")[1].split("SRC_ID")[0].replace("\\", " ").split()

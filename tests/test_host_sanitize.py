@@ -1,7 +1,7 @@
 """The host planning code of libmirsha (alias detection, size-class order,
 block partition, direct-mode lane planner) under AddressSanitizer and
 UndefinedBehaviorSanitizer, on CPU: tests/cpp/host_planning_asan.cpp includes
-mirbft_amd/csrc/mirsha.cpp, stubs the kernel launchers, and checks every result
+mirbft_amd/csrc/host_plan.hpp (HIP-free: plain g++, no stub), and checks every result
 against a plain reference over random and edge-case inputs. (GPU sanitizers are
 not available on this pool; host code is where they apply.)"""
 import os

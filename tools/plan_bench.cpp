@@ -1,41 +1,19 @@
 // Host-only timing of the planning steps of msha_digest_batch on a c5-shaped
 // batch (8M messages: 70% 512 B, 25% k x 32 B, 5% aliases of 100 ~49 KB
-// payloads). No GPU: the helpers are compiled straight from mirsha.cpp. First
+// payloads). No GPU: the helpers are those of mirbft_amd/csrc/host_plan.hpp, which is
+// HIP-free. First
 // the pageable path's host planning (alias table, size-class order, placement),
 // then the pinned path's whole host share (the scan, and per shard the marking
 // pass and granule map; its lanes are planned on the GPU, plan.hip) at 1 and 8
 // shards, each shard on the pool the library would give it.
-// Build: g++ -O3 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wno-subobject-linkage \
-//        -o tools/plan_bench tools/plan_bench.cpp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -pthread
-#include "../mirbft_amd/csrc/mirsha.cpp"
+// Build: g++ -O3 -std=c++17 -o tools/plan_bench tools/plan_bench.cpp -pthread
+#include "../mirbft_amd/csrc/host_plan.hpp"
 
 #include <cstdio>
 #include <map>
 #include <random>
 
-// The launchers live in kernels.hip; this host-only harness never launches.
-namespace msha {
-bool plan_split(uint64_t, int, int, SplitPlan*, int) { return false; }
-hipError_t launch_plan(const PlanArgs&, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_digest_batch(const uint8_t*, const uint64_t*, const uint64_t*, const uint32_t*,
-                               const uint32_t*, uint64_t, uint8_t*, uint32_t*, int, int, hipStream_t,
-                               const SplitPlan*, LaunchKind*, const LaneGate*) {
-  return hipErrorNotSupported;
-}
-hipError_t launch_fold_plan(const FoldArgs&, hipStream_t, hipEvent_t) { return hipErrorNotSupported; }
-hipError_t launch_fold_longs(const FoldArgs&, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_fold_fill(const uint32_t*, uint64_t, uint8_t*, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_clock_probe(uint32_t, uint32_t, uint64_t*, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
-bool uses_coop(uint64_t, int, int) { return false; }
-hipError_t launch_digest_uniform(const uint8_t*, uint64_t, uint64_t, uint64_t, uint8_t*, uint32_t*, int,
-                                 hipStream_t, LaunchKind*) {
-  return hipErrorNotSupported;
-}
-hipError_t launch_digest_of_digests(const uint8_t*, const uint32_t*, const uint64_t*, uint64_t, uint8_t*,
-                                    uint32_t*, hipStream_t, const SplitPlan*, LaunchKind*) {
-  return hipErrorNotSupported;
-}
-}  // namespace msha
+using namespace msha;
 
 int main(int argc, char** argv) {
   const uint64_t n = argc > 1 ? strtoull(argv[1], nullptr, 0) : (1ull << 23);
