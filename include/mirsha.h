@@ -231,6 +231,35 @@ enum { MSHA_PLAN_FOLD_ALIASES = 1u };
 int msha_digest_batch_device_planned(msha_ctx* ctx, const uint8_t* d_arena, const uint64_t* d_off,
                                      const uint64_t* d_len, uint64_t n, uint32_t flags, uint8_t* d_out,
                                      void* stream);
+/*
+ * The plan of the last msha_digest_batch_device_planned call of the context (ABI 10,
+ * additive: MSHA_HAS_PLANNED_READ tells a build that has it). Diagnostic, synchronous,
+ * like msha_parts_plan_read_order: waits for the device, then copies the planner's
+ * counters into *out, the lane order (message indices, position 0 first, 0xFFFFFFFF at
+ * the `n - lanes` positions past the last lane) into order[0 .. min(n, order_cap)) and the
+ * early head's list into longs[0 .. min(long_listed, long_cap, longs_cap)). order and longs
+ * may be NULL when their cap is 0. Before any planned call: MSHA_OK with out->n == 0.
+ * The lanes are ordered by descending class (exact length below 1 KiB, exact block count
+ * below 4,096 blocks, floor(log2 blocks) above); inside a class any order may come back.
+ */
+#define MSHA_HAS_PLANNED_READ 1
+typedef struct {
+  uint64_t n;            /* messages of the last planned call; 0: none yet */
+  uint32_t folded;       /* it had MSHA_PLAN_FOLD_ALIASES */
+  uint32_t lanes;        /* messages that are hashed: order[0 .. lanes) */
+  uint32_t head;         /* positions at the front the lane kernel skips: the head kernel's */
+  uint32_t early;        /* the early head's lanes (0: none, or it stood down) */
+  uint32_t late;         /* the late head's lanes (0 when the early head has the long lanes) */
+  uint32_t long_lanes;   /* lanes of >= 256 blocks, as the scan counted them */
+  uint32_t long_listed;  /* distinct long payloads the early head's pass listed */
+  uint32_t gate;         /* the early head's first decision (0: it stood down before listing) */
+  uint32_t long_cap, head_cap, head_per_wg;  /* what the call gave its kernels: the early head's
+                            and the head's most lanes (long_cap 0: no early head was tried),
+                            and the messages of one head workgroup */
+  uint64_t gave_up;      /* tile look-backs that gave up waiting (folded calls; else 0) */
+} msha_planned_plan;
+int msha_planned_read_plan(msha_ctx* ctx, msha_planned_plan* out, uint32_t* order, uint64_t order_cap,
+                           uint32_t* longs, uint64_t longs_cap);
 /* Uniform layout: message i = d_arena[i*stride : i*stride + msg_len] (stride a
  * multiple of 16; messages may overlap, stride 0 hashes one message n times). */
 int msha_digest_uniform_device(msha_ctx* ctx, const uint8_t* d_arena, uint64_t stride,

@@ -33,6 +33,7 @@ MSHA_KERNEL_LANE = 1
 MSHA_KERNEL_COOP = 2
 MSHA_STREAM_STATE_BYTES = 108
 MSHA_PARTS_FOLD = 1
+MSHA_HAS_PLANNED_READ = 1
 MSHA_HAS_PARTS_CONCAT = 1
 MSHA_HAS_PARTS_ROUTED = 1
 MSHA_HAS_VERIFY_DEVICE = 1
@@ -128,6 +129,24 @@ class MshaStreamsStats(ctypes.Structure):
         ("last_load_mode", ctypes.c_uint32),
         ("last_lanes", ctypes.c_uint32),
         ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
+class MshaPlannedPlan(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("folded", ctypes.c_uint32),
+        ("lanes", ctypes.c_uint32),
+        ("head", ctypes.c_uint32),
+        ("early", ctypes.c_uint32),
+        ("late", ctypes.c_uint32),
+        ("long_lanes", ctypes.c_uint32),
+        ("long_listed", ctypes.c_uint32),
+        ("gate", ctypes.c_uint32),
+        ("long_cap", ctypes.c_uint32),
+        ("head_cap", ctypes.c_uint32),
+        ("head_per_wg", ctypes.c_uint32),
+        ("gave_up", ctypes.c_uint64),
     ]
 
 
@@ -319,6 +338,8 @@ SIGNATURES = {
     "msha_digest_batch_device_planned": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p,
                                                         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
                                                         ctypes.c_void_p, ctypes.c_void_p]),
+    "msha_planned_read_plan": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaPlannedPlan), _u32p, ctypes.c_uint64, _u32p,
+                                              ctypes.c_uint64]),
     "msha_digest_uniform_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
     "msha_digest_of_digests_device": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p,

@@ -113,6 +113,14 @@ struct Device {
   hipStream_t head_stream = nullptr;  // a folded call's early head (FoldArgs::longs)
   hipEvent_t ev_longs = nullptr, ev_join2 = nullptr;
   uint32_t f_epoch = 0;  // the alias table's epoch tag of the last folded call (plan.hip fold_claim)
+  // What msha_planned_read_plan needs of the last planned call (n 0: none yet): the rest
+  // it reads from f_cnt (info; gave_up_at: the look-back's give-up count, in bytes),
+  // f_order and f_longs.
+  struct LastPlanned {
+    uint64_t n = 0, gave_up_at = 0;
+    bool fold = false, early = false;
+    uint32_t long_cap = 0, head_cap = 0, head_per_wg = 0;
+  } f_last;
   DevBuf probe;  // msha_clock_probe: stamps + sink
   // direct path heads (launch_head): their digests, lane-indexed; read back with
   // their lanes' digest slots into h_head ([digests | slots])

@@ -232,7 +232,18 @@ int msha_digest_batch_device_planned(msha_ctx* ctx, const uint8_t* d_arena, cons
     // 1,427-block chain starting at the end). The variants that moved the list into
     // the insert or dropped the late head lost: DESIGN.md §(d) "The folded planner".
     // 1. the memsets
+    d.f_last.n = 0;  // (msha_planned_read_plan: the scratch may be regrown from here on)
     const msha::FoldArgs fa = prepare_plan(d, k, d_off, d_len, n, fold, st);
+    d.f_last.n = n;  // and now describes this call
+    d.f_last.fold = fold;
+    d.f_last.early = k.early;
+    d.f_last.long_cap = fa.long_cap;
+    d.f_last.head_cap = fa.head_cap;
+    d.f_last.head_per_wg = fa.head_per_wg;
+    d.f_last.gave_up_at =
+        fold ? (uint64_t)(reinterpret_cast<const uint8_t*>(fa.tstat + (n + msha::kPlanTile - 1) / msha::kPlanTile) -
+                          d.f_cnt.as<uint8_t>())
+             : 0;
     if (k.early) {
       // 2. the head stream's fork
       HIPCHK(hipEventRecord(d.ev_longs, st));
@@ -312,6 +323,41 @@ int msha_digest_batch_device_planned(msha_ctx* ctx, const uint8_t* d_arena, cons
       fprintf(stderr, "[msha] planned device call: %llu messages, %u lanes, head %u\n", (unsigned long long)n,
               info[0], info[1]);
     }
+  });
+}
+
+int msha_planned_read_plan(msha_ctx* ctx, msha_planned_plan* out, uint32_t* order, uint64_t order_cap,
+                           uint32_t* longs, uint64_t longs_cap) {
+  if (!ctx || !out || (order_cap && !order) || (longs_cap && !longs)) return MSHA_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  *out = msha_planned_plan{};
+  if (ctx->devs.empty() || ctx->devs[0].f_last.n == 0) return MSHA_OK;
+  return guarded(ctx, [&] {
+    Device& d = ctx->devs[0];
+    const Device::LastPlanned& lp = d.f_last;
+    HIPCHK(hipSetDevice(d.id));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t info[32];
+    HIPCHK(hipMemcpy(info, d.f_cnt.p, sizeof info, hipMemcpyDeviceToHost));
+    out->n = lp.n;
+    out->folded = lp.fold;
+    out->lanes = info[0];
+    out->head = info[1];
+    out->early = info[4];
+    out->late = info[5];
+    out->long_lanes = info[16];
+    out->long_listed = info[2];
+    out->gate = info[6];
+    out->long_cap = lp.long_cap;
+    out->head_cap = lp.head_cap;
+    out->head_per_wg = lp.head_per_wg;
+    if (lp.fold)
+      HIPCHK(hipMemcpy(&out->gave_up, d.f_cnt.as<uint8_t>() + lp.gave_up_at, 8, hipMemcpyDeviceToHost));
+    const uint64_t k = std::min(lp.n, order_cap);
+    if (k) HIPCHK(hipMemcpy(order, d.f_order.p, 4 * k, hipMemcpyDeviceToHost));
+    // (f_longs exists only for calls with an early head to try: long_cap 0 otherwise)
+    const uint64_t kl = lp.early ? std::min<uint64_t>(std::min(info[2], lp.long_cap), longs_cap) : 0;
+    if (kl) HIPCHK(hipMemcpy(longs, d.f_longs.p, 4 * kl, hipMemcpyDeviceToHost));
   });
 }
 

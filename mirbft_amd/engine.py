@@ -283,6 +283,21 @@ class Engine:
                                                                1 if fold else 0, out.data_ptr(),
                                                                self._stream_ptr(stream)))
 
+    def planned_read_plan(self):
+        """msha_planned_read_plan: the last digest_batch_device_planned call's plan ->
+        (the counters as a dict, the lane order over all n positions, the early head's
+        list). Waits for the device; a diagnostic. Before any planned call n is 0 and
+        both arrays are empty."""
+        p = L.MshaPlannedPlan()
+        self._check(self._lib.msha_planned_read_plan(self._ctx, ctypes.byref(p), None, 0, None, 0))
+        order = np.empty(p.n, dtype=np.uint32)
+        longs = np.empty(min(p.long_listed, p.long_cap), dtype=np.uint32)
+        if p.n:
+            self._check(self._lib.msha_planned_read_plan(
+                self._ctx, ctypes.byref(p), _p(order, ctypes.c_uint32) if order.size else None, order.size,
+                _p(longs, ctypes.c_uint32) if longs.size else None, longs.size))
+        return {name: getattr(p, name) for name, _ in L.MshaPlannedPlan._fields_}, order, longs
+
     def digest_uniform_device(self, arena, stride: int, msg_len: int, n: int, out, stream=None) -> None:
         self._check_device_args(n, out, arena=arena)
         self._check(self._lib.msha_digest_uniform_device(self._ctx, arena.data_ptr(), stride, msg_len, n,

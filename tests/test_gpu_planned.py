@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import planned_matrix
 from mirbft_amd import MshaError
 from mirbft_amd import workloads as W
 from oracle import oracle
@@ -441,14 +442,10 @@ def test_tile_backrefs(engine, backrefs):
 
 
 def _model_lanes(w):
-    """The folded planner's lane count (plan.hip k_fold_insert) on the host: a message is
-    fresh, a lane without a claim, when it is not long (>= 256 blocks: the early head's) and
-    its offset is strictly above every earlier one's (message 0 counts as above); the others
-    claim (off, len) in the alias table, one claimant per distinct key a lane."""
-    blocks = (w.len >> np.uint64(6)) + np.where((w.len & np.uint64(63)) < 56, 1, 2).astype(np.uint64)
-    off = w.off.astype(np.int64)
-    fresh = (blocks < 256) & (off > np.r_[-1, np.maximum.accumulate(off)[:-1]])
-    return int(fresh.sum()) + len(np.unique(np.stack([w.off[~fresh], w.len[~fresh]], 1), axis=0))
+    """The folded planner's lane count on the host: the rule lives in tests/planned_matrix.py
+    (fresh messages, plus one claimant per distinct key among the rest; a call of this size
+    tries an early head, so a long message is never fresh)."""
+    return planned_matrix.model_lanes(w.off, w.len, early_on=True)
 
 
 @pytest.mark.parametrize("case", ["backrefs", "c5"])
