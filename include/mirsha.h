@@ -1280,6 +1280,167 @@ typedef struct {
 int msha_get_group_stats(const msha_ctx* ctx, msha_group_stats* out);
 
 /*
+ * Device digest maps (ABI 10, additive: MSHA_HAS_DIGEST_MAP tells a build that has them).
+ * msha_group_digests_device answers for the n slots of one call and keeps nothing. The
+ * maps it stands for fill up message by message, over many ActionLists: a sequence's
+ * prepares and commits (pkg/statemachine/sequence.go:73-74, 271-277, 331-340), a
+ * checkpoint's values (checkpoints.go:264-290), the request acks per (client, reqNo)
+ * (client_hash_disseminator.go:346-349, 415-504); and what the state machine acts on is
+ * the moment a key's count crosses a quorum (agreements := s.prepares[string(s.digest)]
+ * against someCorrectQuorum / intersectionQuorum). A device digest map is that map kept in
+ * HBM across calls: stable entry ids, running counts, and a per-call report of the keys
+ * whose count crossed a threshold. Measured times, against regrouping everything seen so
+ * far and against the download with a host map, and where it loses:
+ * profiles/dmap/README.md.
+ *
+ * THE OBJECT. msha_dmap_create allocates, on the context's first device, everything the
+ * map will ever hold, for max_keys in [1, 2^30] keys: the key store (uint32 scope[max_keys]
+ * and 32-byte digest rows, 16-byte aligned) and uint32 count[max_keys], both indexed by
+ * entry id; an open-addressing table uint32[capacity], capacity = bit_ceil(2 max_keys) and
+ * at least 64, holding EMPTY or an id; and a small head of 64-bit words (`entries`, and
+ * the words the kernels hand to one another): 4 bytes of scope, 32 of digest and 4 of
+ * count a key, 40, plus 4 a table position, 8 to 16 a key: 48 to 56 bytes a key in all
+ * (48 * 2^20 bytes and the head at max_keys = 2^20). Each of the five arrays is rounded up
+ * to 256 bytes and the table has at least 64 positions, so a map of a few keys is about
+ * 1.3 KiB whatever max_keys says. A map is destroyed before its context, and every call on
+ * it takes the context's lock. The seed of its keyed hash is 64 bits drawn at create, for the
+ * reason given under CANONICAL of the entry above.
+ *
+ * An ENTRY ID is a key's position in order of first occurrence over the map's whole life
+ * since the last clear. It never changes. There is no erase (open addressing would need
+ * tombstones): a caller drops a whole map, a checkpoint window, with msha_dmap_clear_device.
+ * Multi-GPU maps and per-sender deduplication of votes are out of scope as well: a slot is
+ * a vote, and the caller hands each vote in once.
+ *
+ * msha_dmap_add_device.
+ *
+ * KEY. As in msha_group_digests_device: slot i's key is (d_scope ? d_scope[i] : 0, the 32
+ * bytes at d_digests + 32 i). Equality is the full 36-byte compare, always: between the
+ * slots of the call, and against the stored keys.
+ *
+ * ID. d_id[i] is the entry id of slot i's key. Keys already in the map keep their id. Keys
+ * new in this call get entries_before + r, r their rank by first occurrence in this call
+ * AMONG THE NEW KEYS: existing keys that lie between two new ones use up no number.
+ *
+ * COUNTS. d_before[i] is the key's count before the call, 0 for a new key; d_after[i] is
+ * d_before[i] plus the slots of this call that hold the key, and becomes the key's count.
+ * The count saturates at 2^32 - 1. Both arrays may be NULL.
+ *
+ * CROSSED. A key crossed when threshold > 0 && before < threshold && threshold <= after.
+ * d_crossed_slot[0 .. listed) holds the call's leader slot of each crossing key, the key's
+ * smallest slot in this call, in ascending order; listed = min(crossed, crossed_cap).
+ * Entries at and past listed are not written. d_crossed_slot may be NULL with crossed_cap
+ * 0. From a leader slot the caller has d_id, d_scope and the digest in its own arrays.
+ *
+ * FULL: ALL OR NOTHING. The call is refused whole if entries_before + added > max_keys
+ * (added: the new keys of this call). result.full is then 1 and every d_id[i] is
+ * 0xFFFFFFFF; d_before and d_after are still written as described, for inspection (new
+ * keys have before 0); crossed is 0 and nothing is listed; and no byte of the map changes:
+ * not the table, the keys, the counts or entries. A call that fits exactly succeeds.
+ *
+ * RESULT. *d_result (device memory) is written whole by every call that launches. When
+ * full, max_count and max_id are 0.
+ *
+ * CANONICAL. Every output, and every byte msha_dmap_read returns, is a function of the
+ * sequence of calls alone: none depends on the seed, on where a key landed in the table,
+ * or on the order workgroups ran in.
+ *
+ * READ AND WRITE CONTRACT. Read: the 32 n bytes of d_digests, as whole 16-byte pieces (a
+ * row may be read several times), and the n entries of d_scope. Written: d_id and the two
+ * optional arrays, n entries each, the first listed entries of d_crossed_slot, and
+ * *d_result. Nothing else of the caller's is touched. d_result is 8-byte aligned and the
+ * 32-bit arrays 4-byte aligned, as their types say; the outputs must not overlap the
+ * inputs or one another.
+ *
+ * Checked on the host (MSHA_ERR_INVALID_ARG, each with a text): null pointers; d_digests
+ * not MSHA_DEVICE_ALIGN-aligned; n above 2^30; crossed_cap > 0 with d_crossed_slot NULL.
+ * n == 0 returns MSHA_OK and launches nothing (*d_result is left as it was). No bit of the
+ * device error word is used and msha_device_status() is untouched by a map.
+ *
+ * ONE STREAM, capturable: seven kernels go on `stream` (NULL: the context's own), counted
+ * in msha_dmap_stats.launches: the init, insert and resolve of msha_group_digests_device,
+ * on a table of the call's own, find the call's leaders; then find (leaders look their
+ * key up in the map, read-only), scan (one workgroup: the numbers and the decision),
+ * commit (nothing when full) and fill (dmap.hip). There is no memset, no library stream
+ * and no host wait, every dependency is a kernel boundary and no workgroup waits on
+ * another, so the call captures into a HIP graph as a linear chain of seven kernel nodes,
+ * and a replay adds again.
+ *
+ * WORKSPACE. The call's table and per-slot scratch are a workspace the map owns (the
+ * group entry's workspace and counters are untouched by a map call): 4 bytes a position of
+ * the call's table (8 to 16 a slot), 24 bytes a slot and 12 a 256 slots. It follows the
+ * rule of the other device calls' workspaces: it grows only outside stream capture and
+ * never shrinks, a call outside capture is ordered after the map's previous add, whatever
+ * stream that was on, by an event, and on a capturing stream a call that would have to
+ * allocate fails with MSHA_ERR_INVALID_ARG and says to make one call of this size outside
+ * the capture first; the map is unchanged then. Ordering against finds and clears on other
+ * HIP streams is the caller's.
+ *
+ * msha_dmap_find_device: one kernel, a lane a slot, read-only. d_id[i] and d_count[i]
+ * (d_count may be NULL) are the id and the count of slot i's key, or 0xFFFFFFFF and 0 if
+ * the map does not hold it. It changes nothing and captures as one kernel node. Host
+ * checks as for add. msha_dmap_clear_device: one kernel; the table goes to EMPTY and
+ * entries to 0 (counts and keys need no clearing: new ids overwrite them).
+ *
+ * msha_dmap_size and msha_dmap_read take host memory and wait for the device, as
+ * msha_dstreams_length and _export do. read copies entries first_id .. first_id + k: k
+ * scopes, 32 k digest bytes and k counts (each array may be NULL); a range that reaches
+ * past entries is MSHA_ERR_INVALID_ARG.
+ *
+ * Two diagnostics, read at each call: MSHA_DMAP_SEED replaces the map's seed, and
+ * MSHA_DMAP_FORCE_HOME=h gives every key the home position h mod capacity in the map's
+ * table, so that a test reaches the probe chain and its wrap-around at small shapes. A key
+ * is looked for where the values in force would have put it, so each keeps one value from
+ * a clear (or create) to the next; then neither changes an output byte. MSHA_GROUP_SEED
+ * and MSHA_GROUP_FORCE_HOME keep acting on the call's table.
+ */
+#define MSHA_HAS_DIGEST_MAP 1
+typedef struct msha_dmap msha_dmap;
+typedef struct {
+  uint64_t n;          /* slots added */
+  uint64_t entries;    /* keys in the map after the call */
+  uint64_t added;      /* keys of this call the map did not hold */
+  uint64_t full;       /* 1: the call was refused whole, the map is as it was */
+  uint64_t crossed;    /* keys whose count crossed the threshold in this call */
+  uint64_t listed;     /* min(crossed, crossed_cap): entries written to d_crossed_slot */
+  uint64_t max_count;  /* the largest count after the call among the keys it touched */
+  uint64_t max_id;     /* the smallest entry id that has it */
+} msha_dmap_result;    /* device memory, written whole by every call that launches */
+int msha_dmap_create(msha_ctx* ctx, uint64_t max_keys, msha_dmap** out);
+void msha_dmap_destroy(msha_dmap* map);
+int msha_dmap_add_device(msha_dmap* map,
+                         const uint8_t* d_digests, uint64_t n,
+                         const uint32_t* d_scope,            /* may be NULL */
+                         uint32_t threshold,
+                         uint32_t* d_id,
+                         uint32_t* d_before, uint32_t* d_after,  /* each may be NULL */
+                         uint32_t* d_crossed_slot, uint64_t crossed_cap,
+                         msha_dmap_result* d_result, void* stream);
+int msha_dmap_find_device(msha_dmap* map,
+                          const uint8_t* d_digests, uint64_t n,
+                          const uint32_t* d_scope,           /* may be NULL */
+                          uint32_t* d_id,
+                          uint32_t* d_count,                 /* may be NULL */
+                          void* stream);
+int msha_dmap_clear_device(msha_dmap* map, void* stream);
+int msha_dmap_size(msha_dmap* map, uint64_t* entries);
+int msha_dmap_read(msha_dmap* map, uint64_t first_id, uint64_t k,
+                   uint32_t* scope_out, uint8_t* digests_out, uint32_t* count_out);
+/* Counters of one map (no other entry's counters move with it). */
+typedef struct {
+  uint64_t adds;          /* add calls that enqueued their launches */
+  uint64_t finds;         /* find calls */
+  uint64_t clears;        /* clear calls (the one inside create is not counted) */
+  uint64_t digests;       /* slots of the adds and finds (n) */
+  uint64_t launches;      /* kernel launches: seven an add, one a find, one a clear */
+  uint64_t capacity;      /* table positions: bit_ceil(2 max_keys), at least 64 */
+  double last_kernel_ms;  /* the last call's kernels timed by HIP events, only under MSHA_PARTS_TIMING=1
+                             (read at each call; the call then waits for its kernels; never while
+                             `stream` is being captured); otherwise 0 */
+} msha_dmap_stats;
+int msha_dmap_get_stats(const msha_dmap* map, msha_dmap_stats* out);
+
+/*
  * Host-only helpers (no GPU needed).
  * msha_blocks_for_len: number of 64-byte compressions for an L-byte message,
  *   floor(L/64) + (L%64 < 56 ? 1 : 2)  (FIPS 180-4 5.1.1 padding).

@@ -8,7 +8,9 @@ from .engine import Engine, MshaError, blocks_for_len, device_count, pack_parts,
 from .processor import (Action, ActionHashRequest, ActionList, EventHashResult, EventList, GPUHasher,
                         HashOrigin, HashOriginBatch, HashOriginEpochChange, HashOriginVerifyBatch,
                         ProcessHashActions, ProcessorError, action_hash, checkpoint_hashes,
-                        dedupe_digests_device, tally_digests_device, verify_batches_device)
+                        dedupe_digests_device, tally_digests_device, tally_into_map_device,
+                        verify_batches_device)
+from .digest_map import DeviceDigestMap
 from .streams import StreamSet
 from .streams_device import DeviceStreamSet
 
@@ -18,5 +20,5 @@ __all__ = [
     "HashOrigin", "HashOriginBatch", "HashOriginEpochChange", "HashOriginVerifyBatch",
     "ProcessHashActions", "ProcessorError", "action_hash", "checkpoint_hashes",
     "verify_batches_device", "tally_digests_device", "dedupe_digests_device",
-    "StreamSet", "DeviceStreamSet",
+    "tally_into_map_device", "StreamSet", "DeviceStreamSet", "DeviceDigestMap",
 ]

@@ -38,6 +38,7 @@ MSHA_HAS_PARTS_CONCAT = 1
 MSHA_HAS_PARTS_ROUTED = 1
 MSHA_HAS_VERIFY_DEVICE = 1
 MSHA_HAS_GROUP_DEVICE = 1
+MSHA_HAS_DIGEST_MAP = 1
 MSHA_ROUTE_LONG_BLOCKS_DEFAULT = 64
 MSHA_ROUTE_LONG_BYTES_DEFAULT = 32 << 20
 MSHA_HAS_STREAMS_DEVICE = 1
@@ -224,6 +225,31 @@ class MshaGroupStats(ctypes.Structure):
     ]
 
 
+class MshaDmapResult(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("entries", ctypes.c_uint64),
+        ("added", ctypes.c_uint64),
+        ("full", ctypes.c_uint64),
+        ("crossed", ctypes.c_uint64),
+        ("listed", ctypes.c_uint64),
+        ("max_count", ctypes.c_uint64),
+        ("max_id", ctypes.c_uint64),
+    ]
+
+
+class MshaDmapStats(ctypes.Structure):
+    _fields_ = [
+        ("adds", ctypes.c_uint64),
+        ("finds", ctypes.c_uint64),
+        ("clears", ctypes.c_uint64),
+        ("digests", ctypes.c_uint64),
+        ("launches", ctypes.c_uint64),
+        ("capacity", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
 class MshaRouteOpts(ctypes.Structure):
     _fields_ = [
         ("long_blocks", ctypes.c_uint32),
@@ -395,6 +421,17 @@ SIGNATURES = {
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                                  ctypes.c_void_p, ctypes.c_void_p]),
     "msha_get_group_stats": (ctypes.c_int, [_ctxp, ctypes.POINTER(MshaGroupStats)]),
+    "msha_dmap_create": (ctypes.c_int, [_ctxp, ctypes.c_uint64, ctypes.POINTER(_setp)]),
+    "msha_dmap_destroy": (None, [_setp]),
+    "msha_dmap_add_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
+    "msha_dmap_find_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "msha_dmap_clear_device": (ctypes.c_int, [_setp, ctypes.c_void_p]),
+    "msha_dmap_size": (ctypes.c_int, [_setp, _u64p]),
+    "msha_dmap_read": (ctypes.c_int, [_setp, ctypes.c_uint64, ctypes.c_uint64, _u32p, _u8p, _u32p]),
+    "msha_dmap_get_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaDmapStats)]),
     "msha_hash_actions_device_routed": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                                        ctypes.c_uint64, ctypes.POINTER(MshaRouteOpts),
@@ -487,6 +524,7 @@ _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip",
               "stream_chain.hpp", "stream_chain.hip", "stream_write.hpp", "stream_jobs_route.hpp",
               "verify.hpp", "verify.hip", "verify.cpp",
               "group.hpp", "group.hip", "group.cpp",
+              "dmap.hpp", "dmap.hip", "dmap.cpp",
               "parts_concat.hpp", "parts_concat.hip", "parts_concat.cpp")
 
 

@@ -1,6 +1,6 @@
 // What the device entries of several launches share (msha_hash_actions_device_planned and
 // _routed, msha_dstreams_write_jobs_device and _write_routed_device,
-// msha_group_digests_device): the workspace each
+// msha_group_digests_device, msha_dmap_add_device): the workspace each
 // of them owns, what the two parts entries keep in the context, and the arguments they
 // read alike. Host-only.
 //

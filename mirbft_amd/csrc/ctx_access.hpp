@@ -2,8 +2,8 @@
 // is defined there): its lock, its first device, its error text and what the device
 // entries keep in it (the states by name only: call_workspace.hpp defines them). Defined
 // at the end of ctx.cpp; used, through host_call.hpp, by streams.cpp, parts.cpp,
-// parts_plan.cpp, parts_concat.cpp, parts_route.cpp, stream_device.cpp, verify.cpp and
-// group.cpp. The host paths and device_batch.cpp include ctx.hpp and see the context itself.
+// parts_plan.cpp, parts_concat.cpp, parts_route.cpp, stream_device.cpp, verify.cpp,
+// group.cpp and dmap.cpp. The host paths and device_batch.cpp include ctx.hpp and see the context itself.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

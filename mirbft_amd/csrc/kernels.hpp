@@ -544,6 +544,56 @@ hipError_t launch_group_scan(const GroupArgs& a, hipStream_t st);
 hipError_t launch_group_rank(const GroupArgs& a, hipStream_t st);
 hipError_t launch_group_fill(const GroupArgs& a, hipStream_t st);
 
+// A device digest map (dmap.hip, msha_dmap_*): the keys, their counts and the table that
+// finds them live in the map's own allocation (dmap.hpp Store) from create to destroy. An
+// add groups the call's slots with launch_group_init, _insert and _resolve on a GroupArgs
+// that points into the map's per-call workspace (dmap.hpp CallLayout: first, members), and
+// then only the leaders touch the map: find (read-only), scan (one workgroup: the numbers
+// and the decision), commit (nothing when the call is refused) and fill. Seven kernels on
+// one stream, every dependency a kernel boundary, no device error bit and no host wait:
+// capturable.
+struct DmapArgs {
+  const uint8_t* digests = nullptr;
+  uint64_t n = 0;
+  const uint32_t* scope = nullptr;     // n, or null: every scope 0
+  uint32_t threshold = 0;
+  uint32_t* id = nullptr;              // n
+  uint32_t* before = nullptr;          // n, or null
+  uint32_t* after = nullptr;           // n, or null
+  uint32_t* crossed_slot = nullptr;    // crossed_cap, null when that is 0
+  uint64_t crossed_cap = 0;
+  uint64_t* result = nullptr;          // msha_dmap_result as eight words
+  // the call's workspace: dmap.hpp CallLayout
+  const uint32_t* first = nullptr;     // n: the smallest slot of the call with slot i's key
+  const uint32_t* members = nullptr;   // n: at a leader, the call's slots with its key
+  uint32_t* lead_id = nullptr;         // n: at a leader, the key's id (kNew until commit numbers it)
+  uint32_t* lead_pos = nullptr;        // n: at a leader, where find stopped
+  uint32_t* lead_before = nullptr;     // n: at a leader, the key's count before the call
+  uint32_t* tot_new = nullptr;         // tiles(n)
+  uint32_t* tot_cross = nullptr;       // tiles(n)
+  uint64_t* best = nullptr;            // one word, zeroed by k_group_init: the largest (after, ~id)
+  // the map: dmap.hpp Store
+  uint64_t* head = nullptr;
+  uint32_t* table = nullptr;
+  uint32_t* key_scope = nullptr;
+  uint8_t* key_digests = nullptr;
+  uint32_t* count = nullptr;
+  uint64_t capacity = 0;               // table positions: dmap::capacity(max_keys)
+  uint64_t max_keys = 0;
+  uint64_t seed = 0;                   // of the hash that places keys in the map's table
+  uint32_t force_home = 0, force_at = 0;  // MSHA_DMAP_FORCE_HOME: every key's home is force_at
+};
+// k_dmap_find, _scan, _commit, _fill, in this order behind group's first three; one launch each.
+hipError_t launch_dmap_find(const DmapArgs& a, hipStream_t st);
+hipError_t launch_dmap_scan(const DmapArgs& a, hipStream_t st);
+hipError_t launch_dmap_commit(const DmapArgs& a, hipStream_t st);
+hipError_t launch_dmap_fill(const DmapArgs& a, hipStream_t st);
+// k_dmap_lookup (msha_dmap_find_device): a lane a slot, read-only; id and count (count may
+// be null) of slot i's key, or kNoId and 0. k_dmap_clear: the table EMPTY, entries 0.
+// Both read the map's fields of a alone, and lookup digests, n, scope, id and after (the count).
+hipError_t launch_dmap_lookup(const DmapArgs& a, hipStream_t st);
+hipError_t launch_dmap_clear(const DmapArgs& a, hipStream_t st);
+
 // Clock probe (msha_clock_probe): `workgroups` x 256 lanes compress `blocks`
 // register-resident blocks each; stamps gets (memtime, memrealtime) at start and
 // end per workgroup, 4 words each.

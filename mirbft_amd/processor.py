@@ -201,6 +201,13 @@ class GPUHasher:
         from .streams_device import DeviceStreamSet
         return DeviceStreamSet(self.engine, n)
 
+    def new_device_digest_map(self, max_keys: int):
+        """A digest-keyed tally of up to max_keys keys kept in device memory across calls
+        (DeviceDigestMap): stable entry ids, running counts, and for each call the keys
+        whose count crossed a threshold."""
+        from .digest_map import DeviceDigestMap
+        return DeviceDigestMap(self.engine, max_keys)
+
     def hash_batch(self, actions: Sequence[Sequence[bytes]]) -> List[bytes]:
         return self.engine.hash_actions(actions)
 
@@ -379,6 +386,44 @@ def tally_digests_device(hasher: GPUHasher, digests, scope=None, group_cap: int 
     _, groups, listed, max_count, max_group = (int(x) for x in result.cpu().tolist())
     return (groups, max_count, max_group, first, group, members,
             group_first[:listed] if cap > 0 else empty, group_count[:listed] if cap > 0 else empty)
+
+
+def tally_into_map_device(dmap, digests, scope=None, quorum: int = 0, crossed_cap: int = 64, stream=None):
+    """The same maps filled message by message, over many ActionLists: the n digests of
+    this call are counted into `dmap` (GPUHasher.new_device_digest_map), which keeps every
+    key's entry id and running count in HBM. digests is a uint8 tensor of 32 n bytes and
+    scope an int32 tensor of n entries (None: one map), both on the engine's GPU. Returns
+    (entries, added, full, crossed_slots, ids, before, after): the keys the map holds now,
+    how many of them are new, whether the call was refused whole because they do not fit,
+    the leader slots (ascending, at most crossed_cap) of the keys whose count went from
+    below quorum to at least quorum in this call -- the moment agreements :=
+    s.prepares[string(s.digest)] reaches someCorrectQuorum / intersectionQuorum -- and per
+    slot the key's id and its count before and after. One 64-byte read. stream: a
+    torch.cuda.Stream of the caller's (None: the engine's own)."""
+    import torch
+    eng = dmap._engine
+    n = digests.numel() // 32
+    dev = digests.device
+    ids, before, after = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    cap = int(crossed_cap)
+    slots = torch.empty(cap, dtype=torch.int32, device=dev) if cap > 0 else None
+    empty = torch.empty(0, dtype=torch.int32, device=dev)
+    if n == 0:
+        return dmap.size(), 0, False, empty, ids, before, after
+    result = torch.empty(8, dtype=torch.int64, device=dev)
+    # stream handling as in tally_digests_device: None, or torch's default stream, means
+    # the engine's own stream, and then the whole device is waited for, before and after
+    own = not eng._stream_ptr(stream)
+    if own:
+        torch.cuda.synchronize(dev)
+    dmap.add_device(digests, ids, result, scope=scope, threshold=quorum, before=before, after=after,
+                    crossed_slots=slots, stream=stream)
+    if own or not hasattr(stream, "synchronize"):
+        torch.cuda.synchronize(dev)
+    else:
+        stream.synchronize()
+    _, entries, added, full, _, listed, _, _ = (int(x) for x in result.cpu().tolist())
+    return entries, added, bool(full), slots[:listed] if cap > 0 else empty, ids, before, after
 
 
 def dedupe_digests_device(hasher: GPUHasher, digests, stream=None):
