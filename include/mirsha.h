@@ -1309,8 +1309,9 @@ int msha_get_group_stats(const msha_ctx* ctx, msha_group_stats* out);
  * An ENTRY ID is a key's position in order of first occurrence over the map's whole life
  * since the last clear. It never changes. There is no erase (open addressing would need
  * tombstones): a caller drops a whole map, a checkpoint window, with msha_dmap_clear_device.
- * Multi-GPU maps and per-sender deduplication of votes are out of scope as well: a slot is
- * a vote, and the caller hands each vote in once.
+ * Multi-GPU maps are out of scope as well. In a map made by msha_dmap_create a slot is a
+ * vote, and the caller hands each vote in once; a map that counts each sender once a key
+ * is the vote map of "Device digest maps that count voters" below.
  *
  * msha_dmap_add_device.
  *
@@ -1439,6 +1440,144 @@ typedef struct {
                              `stream` is being captured); otherwise 0 */
 } msha_dmap_stats;
 int msha_dmap_get_stats(const msha_dmap* map, msha_dmap_stats* out);
+
+/*
+ * Device digest maps that count voters (ABI 10, additive: MSHA_HAS_DIGEST_VOTE_MAP tells a
+ * build that has them). A map made by msha_dmap_create counts slots. Two of the maps it
+ * stands for count NODES: the request acks are a set, cr.agreements[source] = struct{}{},
+ * every quorum test is len(cr.agreements) (client_hash_disseminator.go:814-832, 492-500),
+ * the set is asked "has node X acked" (:296, :395, sequence.go:218) and listed as node ids
+ * (:647-649); a checkpoint's values are map[string][]nodeID (checkpoints.go:264-280),
+ * compared with the node's own id (:284). A replica that sends the same ack twice -- a
+ * retransmission, a Byzantine sender, our own ack arriving after we stored the request --
+ * must not move a key towards someCorrectQuorum. A VOTE MAP is a device digest map whose
+ * count for a key is the number of distinct voters that voted for it, the set of voters
+ * kept in HBM beside the key, so that no caller has to download digests to deduplicate
+ * (key, sender) on the host. Measured times, against msha_dmap_add_device over the same
+ * slots and against the download with a host dict of sets: profiles/dmap_vote/README.md.
+ *
+ * THE OBJECT. msha_dmap_create_voters(ctx, max_keys, max_voters, &map): max_keys as for
+ * msha_dmap_create, max_voters in [1, 1024]. The map owns everything a plain map owns, in
+ * the same layout, and behind it a voter mask per entry id: uint32 mask[max_keys][words],
+ * words = ceil(max_voters / 32); bit v % 32 of word v / 32 stands for voter v. The mask
+ * store adds 4 words bytes a key to the 48 to 56 of a plain map (4 bytes a key up to 32
+ * voters, 128 at 1024), rounded up to 256 bytes like the other arrays. A new key's mask is
+ * empty. INVARIANT: count[id] == popcount(mask[id]) at every kernel boundary outside a
+ * vote call. msha_dmap_add_device on a vote map is refused (MSHA_ERR_INVALID_ARG, with a
+ * text): it would break the invariant; on a plain map the three vote entries below are
+ * refused the same way. msha_dmap_find_device, _size, _read, _destroy and _get_stats work
+ * on both kinds unchanged. msha_dmap_clear_device on a vote map empties the masks as well:
+ * still one kernel, still one launch counted.
+ *
+ * msha_dmap_vote_device. KEY and ID exactly as in msha_dmap_add_device (first-occurrence
+ * numbering among the new keys, ids stable). d_voter[i] (uint32) is slot i's sender.
+ *
+ * COUNTED. d_counted[i] (uint32, 0 or 1; may be NULL) is 1 iff (a) d_voter[i] < max_voters,
+ * (b) no slot j < i of this call has slot i's key and slot i's voter, and (c) the key's
+ * mask before the call has no bit for d_voter[i] (a new key has an empty mask). Of several
+ * equal votes in one call the smallest slot is the one counted: a function of the inputs,
+ * not of the order lanes ran in.
+ *
+ * COUNTS. d_before[i] is the key's count before the call; d_after[i] is d_before[i] plus
+ * the counted slots of the key in this call, and becomes the key's count. Nothing
+ * saturates: count <= max_voters. A key none of whose slots is counted is still entered
+ * and keeps or gets its id; its count may be 0, if all its voters were out of range.
+ *
+ * CROSSED. threshold > 0 && before < threshold && threshold <= after on these counts;
+ * d_crossed_slot[0 .. listed) holds the leader slots of the crossing keys in ascending
+ * order, listed = min(crossed, crossed_cap), exactly as for add.
+ *
+ * FULL: ALL OR NOTHING, the rule of add: refused whole when entries_before + added >
+ * max_keys. Every d_id[i] is then 0xFFFFFFFF; d_counted, d_before and d_after are still
+ * written as defined above, read-only facts about the map as it was; crossed is 0 and
+ * nothing is listed; and no byte of the map changes: not the table, the keys, the counts,
+ * the masks or entries.
+ *
+ * RESULT. msha_dmap_vote_result is eleven uint64_t: add's eight fields in add's order, then
+ * counted (slots with d_counted 1), repeats (slots with a voter in range that were not
+ * counted) and bad_voters (slots with d_voter[i] >= max_voters: a caller's error made
+ * visible; no bit of the device error word is used and msha_device_status() is untouched).
+ * When full, counted, repeats and bad_voters are still reported; max_count and max_id are
+ * 0 as for add.
+ *
+ * CANONICAL. Every output, and every byte msha_dmap_read and msha_dmap_read_voters return,
+ * is a function of the sequence of calls alone.
+ *
+ * Checked on the host as for add, and: d_voter NULL; a plain map. n == 0 returns MSHA_OK
+ * before any other check and launches nothing. Read in addition to add's: the n entries of
+ * d_voter. Written in addition: the n entries of d_counted.
+ *
+ * ONE STREAM, capturable, a linear chain: TEN kernels go on `stream` (NULL: the context's
+ * own), counted in msha_dmap_vote_stats.launches: the init, insert and resolve of
+ * msha_group_digests_device on the call's own table; find (leaders look their key up,
+ * read-only; the same launch empties the call's pair table); pair (a second table of the
+ * call's joins equal (key, voter) pairs, an entry the smallest slot of its pair); count
+ * (the pair leaders whose bit the key's mask lacks are the counted slots; each key's are
+ * summed); totals; scan (one workgroup: the numbers and the decision); commit (nothing
+ * when full; ids, keys, counts, the crossed list); and fill (the outputs; unless full, each
+ * counted slot sets its bit with a 32-bit atomic OR, a launch behind commit so that a new
+ * id is there first). No memset, no library stream, no host wait, every dependency a
+ * kernel boundary, no workgroup waits on another: the call captures into a HIP graph as a
+ * linear chain of ten kernel nodes, and a replay votes again (and counts nothing new).
+ * The workspace (the add's, then 4 bytes a position of the pair table, 8 to 16 a slot, 12
+ * bytes a slot and 12 a 256 slots) follows add's rule; a capture that would have to
+ * allocate is refused with the text naming msha_dmap_vote_device, the map unchanged.
+ *
+ * msha_dmap_find_votes_device: one kernel, read-only: find's answers (d_count may be NULL)
+ * plus d_voted[i] = 1 iff the key is held and d_voter[i]'s bit is set; absent keys and
+ * voters out of range give 0: _, ok := cr.agreements[nodeID(id)].
+ * msha_dmap_read_voters: a host read like msha_dmap_read: the k * words mask words of
+ * entries first_id .. first_id + k, with read's range check and message.
+ * msha_dmap_get_vote_stats: vote calls move only this struct; msha_dmap_stats keeps its
+ * layout and its adds, finds and launches do not move with them. A clear counts where it
+ * does on a plain map.
+ *
+ * Diagnostics, read at each call: MSHA_DMAP_SEED and MSHA_DMAP_FORCE_HOME keep their
+ * meaning; MSHA_DMAP_PAIR_FORCE_HOME=h gives every (key, voter) pair the home position h
+ * mod capacity in the call's pair table (capacity bit_ceil(2 n), at least 64). None of
+ * them changes an output byte.
+ *
+ * Out of scope: erase (as above); multi-GPU maps; more than 1024 voters; the Go adapter
+ * and include/mirbft/processor.hpp; any change to msha_dmap_add_device.
+ */
+#define MSHA_HAS_DIGEST_VOTE_MAP 1
+typedef struct {
+  uint64_t n, entries, added, full, crossed, listed, max_count, max_id; /* as msha_dmap_result */
+  uint64_t counted;     /* slots with d_counted 1 */
+  uint64_t repeats;     /* slots with a voter in range that were not counted */
+  uint64_t bad_voters;  /* slots with d_voter[i] >= max_voters */
+} msha_dmap_vote_result; /* device memory, written whole by every call that launches */
+int msha_dmap_create_voters(msha_ctx* ctx, uint64_t max_keys, uint32_t max_voters, msha_dmap** out);
+int msha_dmap_vote_device(msha_dmap* map,
+                          const uint8_t* d_digests, uint64_t n,
+                          const uint32_t* d_scope,           /* may be NULL */
+                          const uint32_t* d_voter,
+                          uint32_t threshold,
+                          uint32_t* d_id,
+                          uint32_t* d_counted,               /* may be NULL */
+                          uint32_t* d_before, uint32_t* d_after,  /* each may be NULL */
+                          uint32_t* d_crossed_slot, uint64_t crossed_cap,
+                          msha_dmap_vote_result* d_result, void* stream);
+int msha_dmap_find_votes_device(msha_dmap* map,
+                                const uint8_t* d_digests, uint64_t n,
+                                const uint32_t* d_scope,     /* may be NULL */
+                                const uint32_t* d_voter,
+                                uint32_t* d_id,
+                                uint32_t* d_count,           /* may be NULL */
+                                uint32_t* d_voted,
+                                void* stream);
+int msha_dmap_read_voters(msha_dmap* map, uint64_t first_id, uint64_t k, uint32_t* masks_out);
+/* Counters of one vote map's vote calls (no other counters move with them). */
+typedef struct {
+  uint64_t votes;         /* vote calls that enqueued their launches */
+  uint64_t vote_finds;    /* find_votes calls */
+  uint64_t slots;         /* slots of the votes and find_votes (n) */
+  uint64_t launches;      /* kernel launches: ten a vote, one a find_votes */
+  uint64_t max_voters;    /* as created; 0 on a plain map */
+  uint64_t mask_words;    /* ceil(max_voters / 32) */
+  double last_kernel_ms;  /* as in msha_dmap_stats: only under MSHA_PARTS_TIMING=1 */
+} msha_dmap_vote_stats;
+int msha_dmap_get_vote_stats(const msha_dmap* map, msha_dmap_vote_stats* out);
 
 /*
  * Host-only helpers (no GPU needed).

@@ -9,6 +9,7 @@ from .processor import (Action, ActionHashRequest, ActionList, EventHashResult, 
                         HashOrigin, HashOriginBatch, HashOriginEpochChange, HashOriginVerifyBatch,
                         ProcessHashActions, ProcessorError, action_hash, checkpoint_hashes,
                         dedupe_digests_device, tally_digests_device, tally_into_map_device,
+                        tally_votes_into_map_device,
                         verify_batches_device)
 from .digest_map import DeviceDigestMap
 from .streams import StreamSet
@@ -20,5 +21,5 @@ __all__ = [
     "HashOrigin", "HashOriginBatch", "HashOriginEpochChange", "HashOriginVerifyBatch",
     "ProcessHashActions", "ProcessorError", "action_hash", "checkpoint_hashes",
     "verify_batches_device", "tally_digests_device", "dedupe_digests_device",
-    "tally_into_map_device", "StreamSet", "DeviceStreamSet", "DeviceDigestMap",
+    "tally_into_map_device", "tally_votes_into_map_device", "StreamSet", "DeviceStreamSet", "DeviceDigestMap",
 ]

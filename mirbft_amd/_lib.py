@@ -39,6 +39,7 @@ MSHA_HAS_PARTS_ROUTED = 1
 MSHA_HAS_VERIFY_DEVICE = 1
 MSHA_HAS_GROUP_DEVICE = 1
 MSHA_HAS_DIGEST_MAP = 1
+MSHA_HAS_DIGEST_VOTE_MAP = 1
 MSHA_ROUTE_LONG_BLOCKS_DEFAULT = 64
 MSHA_ROUTE_LONG_BYTES_DEFAULT = 32 << 20
 MSHA_HAS_STREAMS_DEVICE = 1
@@ -250,6 +251,26 @@ class MshaDmapStats(ctypes.Structure):
     ]
 
 
+class MshaDmapVoteResult(ctypes.Structure):
+    _fields_ = MshaDmapResult._fields_ + [
+        ("counted", ctypes.c_uint64),
+        ("repeats", ctypes.c_uint64),
+        ("bad_voters", ctypes.c_uint64),
+    ]
+
+
+class MshaDmapVoteStats(ctypes.Structure):
+    _fields_ = [
+        ("votes", ctypes.c_uint64),
+        ("vote_finds", ctypes.c_uint64),
+        ("slots", ctypes.c_uint64),
+        ("launches", ctypes.c_uint64),
+        ("max_voters", ctypes.c_uint64),
+        ("mask_words", ctypes.c_uint64),
+        ("last_kernel_ms", ctypes.c_double),
+    ]
+
+
 class MshaRouteOpts(ctypes.Structure):
     _fields_ = [
         ("long_blocks", ctypes.c_uint32),
@@ -432,6 +453,16 @@ SIGNATURES = {
     "msha_dmap_size": (ctypes.c_int, [_setp, _u64p]),
     "msha_dmap_read": (ctypes.c_int, [_setp, ctypes.c_uint64, ctypes.c_uint64, _u32p, _u8p, _u32p]),
     "msha_dmap_get_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaDmapStats)]),
+    "msha_dmap_create_voters": (ctypes.c_int, [_ctxp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(_setp)]),
+    "msha_dmap_vote_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
+    "msha_dmap_find_votes_device": (ctypes.c_int, [_setp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p]),
+    "msha_dmap_read_voters": (ctypes.c_int, [_setp, ctypes.c_uint64, ctypes.c_uint64, _u32p]),
+    "msha_dmap_get_vote_stats": (ctypes.c_int, [_setp, ctypes.POINTER(MshaDmapVoteStats)]),
     "msha_hash_actions_device_routed": (ctypes.c_int, [_ctxp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                                        ctypes.c_uint64, ctypes.POINTER(MshaRouteOpts),
@@ -524,7 +555,7 @@ _SRC_FILES = ("sha256_device.hpp", "kernels.hpp", "kernels.hip", "plan.hip",
               "stream_chain.hpp", "stream_chain.hip", "stream_write.hpp", "stream_jobs_route.hpp",
               "verify.hpp", "verify.hip", "verify.cpp",
               "group.hpp", "group.hip", "group.cpp",
-              "dmap.hpp", "dmap.hip", "dmap.cpp",
+              "dmap.hpp", "dmap.hip", "dmap.cpp", "dmap_vote.hpp", "dmap_vote.hip",
               "parts_concat.hpp", "parts_concat.hip", "parts_concat.cpp")
 
 

@@ -272,6 +272,8 @@ __global__ __launch_bounds__(dm::kTile) void k_dmap_clear(DmapArgs a) {
   // capacity is a power of two, at least 64
   if (q < a.capacity / 4) reinterpret_cast<uint4*>(a.table)[q] = make_uint4(dm::kEmpty, dm::kEmpty, dm::kEmpty, dm::kEmpty);
   if (q < dm::kHeadWords) a.head[q] = 0;
+  // a vote map's masks (none on a plain map): every key's set of voters empty
+  if (q < a.mask_quads) reinterpret_cast<uint4*>(a.masks)[q] = make_uint4(0, 0, 0, 0);
 }
 
 // n <= 2^30 (the host's bound): at most 2^22 tiles
@@ -305,8 +307,10 @@ hipError_t launch_dmap_lookup(const DmapArgs& a, hipStream_t st) {
 }
 
 hipError_t launch_dmap_clear(const DmapArgs& a, hipStream_t st) {
-  // capacity <= 2^31: at most 2^21 workgroups
-  const unsigned grid = (unsigned)((a.capacity / 4 + dm::kTile - 1) / dm::kTile);
+  // capacity <= 2^31: at most 2^21 workgroups for the table; the masks of a vote map are
+  // at most 2^30 keys of 32 words, 2^33 quads: 2^25 workgroups. The larger range decides.
+  const uint64_t quads = a.capacity / 4 > a.mask_quads ? a.capacity / 4 : a.mask_quads;
+  const unsigned grid = (unsigned)((quads + dm::kTile - 1) / dm::kTile);
   hipLaunchKernelGGL(k_dmap_clear, dim3(grid), dim3(dm::kTile), 0, st, a);
   return hipGetLastError();
 }

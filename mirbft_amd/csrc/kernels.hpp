@@ -582,6 +582,9 @@ struct DmapArgs {
   uint64_t max_keys = 0;
   uint64_t seed = 0;                   // of the hash that places keys in the map's table
   uint32_t force_home = 0, force_at = 0;  // MSHA_DMAP_FORCE_HOME: every key's home is force_at
+  // a vote map's masks (dmap_vote.hpp VoteStore), null and 0 on a plain map: k_dmap_clear zeroes them
+  uint32_t* masks = nullptr;           // uint32[max_keys][mask_words], by id
+  uint64_t mask_quads = 0;             // 16-byte pieces of the mask store (it is laid out in whole 256 bytes)
 };
 // k_dmap_find, _scan, _commit, _fill, in this order behind group's first three; one launch each.
 hipError_t launch_dmap_find(const DmapArgs& a, hipStream_t st);
@@ -593,6 +596,39 @@ hipError_t launch_dmap_fill(const DmapArgs& a, hipStream_t st);
 // Both read the map's fields of a alone, and lookup digests, n, scope, id and after (the count).
 hipError_t launch_dmap_lookup(const DmapArgs& a, hipStream_t st);
 hipError_t launch_dmap_clear(const DmapArgs& a, hipStream_t st);
+
+// A vote call on a vote map (dmap_vote.hip, msha_dmap_vote_device): a DmapArgs as an add
+// fills it (of which `members` is not read), and what dmap_vote.hpp adds: the voters, the
+// pair table and the per-slot scratch of VoteLayout. Ten kernels on one stream behind one
+// another, the first three group's: capturable as an add is.
+struct DmapVoteArgs : DmapArgs {
+  const uint32_t* voter = nullptr;     // n
+  uint32_t* counted_out = nullptr;     // n, or null
+  uint32_t max_voters = 0, mask_words = 0;
+  // the call's workspace: dmap_vote.hpp VoteLayout
+  uint32_t* pair_table = nullptr;
+  uint32_t* pair_pos = nullptr;        // n
+  uint32_t* counted = nullptr;         // n
+  uint32_t* fresh = nullptr;           // n: at a leader, the counted slots of its key
+  uint32_t* tot_counted = nullptr;     // tiles(n)
+  uint32_t* tot_repeats = nullptr;     // tiles(n)
+  uint32_t* tot_bad = nullptr;         // tiles(n)
+  uint64_t* vhead = nullptr;           // dmap_vote::kHeadWords
+  uint64_t pair_capacity = 0;          // group::capacity(n)
+  uint64_t pair_seed = 0;
+  uint32_t pair_force_home = 0, pair_force_at = 0;  // MSHA_DMAP_PAIR_FORCE_HOME
+};
+// k_vote_find, _pair, _count, _totals, _scan, _commit, _fill, in this order behind group's
+// first three; one launch each. k_vote_lookup (msha_dmap_find_votes_device): k_dmap_lookup
+// plus the voter's bit into counted_out.
+hipError_t launch_vote_find(const DmapVoteArgs& a, hipStream_t st);
+hipError_t launch_vote_pair(const DmapVoteArgs& a, hipStream_t st);
+hipError_t launch_vote_count(const DmapVoteArgs& a, hipStream_t st);
+hipError_t launch_vote_totals(const DmapVoteArgs& a, hipStream_t st);
+hipError_t launch_vote_scan(const DmapVoteArgs& a, hipStream_t st);
+hipError_t launch_vote_commit(const DmapVoteArgs& a, hipStream_t st);
+hipError_t launch_vote_fill(const DmapVoteArgs& a, hipStream_t st);
+hipError_t launch_vote_lookup(const DmapVoteArgs& a, hipStream_t st);
 
 // Clock probe (msha_clock_probe): `workgroups` x 256 lanes compress `blocks`
 // register-resident blocks each; stamps gets (memtime, memrealtime) at start and

@@ -208,6 +208,14 @@ class GPUHasher:
         from .digest_map import DeviceDigestMap
         return DeviceDigestMap(self.engine, max_keys)
 
+    def new_device_vote_map(self, max_keys: int, max_voters: int):
+        """A device digest map whose count for a key is the number of distinct voters, of
+        max_voters (1 .. 1024) nodes, that voted for it (DeviceDigestMap with max_voters):
+        the set of voters is kept in HBM beside the key, so a sender's second ack counts
+        nothing. Filled with tally_votes_into_map_device."""
+        from .digest_map import DeviceDigestMap
+        return DeviceDigestMap(self.engine, max_keys, max_voters)
+
     def hash_batch(self, actions: Sequence[Sequence[bytes]]) -> List[bytes]:
         return self.engine.hash_actions(actions)
 
@@ -424,6 +432,41 @@ def tally_into_map_device(dmap, digests, scope=None, quorum: int = 0, crossed_ca
         stream.synchronize()
     _, entries, added, full, _, listed, _, _ = (int(x) for x in result.cpu().tolist())
     return entries, added, bool(full), slots[:listed] if cap > 0 else empty, ids, before, after
+
+
+def tally_votes_into_map_device(dmap, digests, voter, scope=None, quorum: int = 0, crossed_cap: int = 64, stream=None):
+    """tally_into_map_device for maps that count NODES (the request acks,
+    cr.agreements[source] = struct{}{}; a checkpoint's values): slot i is voter[i]'s vote
+    for the key (scope[i], digest i), counted into the vote map `dmap`
+    (GPUHasher.new_device_vote_map) unless that voter's vote for that key was counted
+    before, in this call at a smaller slot or in an earlier one. voter is an int32 tensor
+    of n node ids. Returns (entries, added, full, crossed_slots, ids, counted, before,
+    after, repeats, bad_voters): as tally_into_map_device, the counts being distinct
+    voters, plus per slot whether it was counted, the slots that were a repeat, and the
+    slots whose voter the map has no bit for (>= max_voters). One 88-byte read."""
+    import torch
+    eng = dmap._engine
+    n = digests.numel() // 32
+    dev = digests.device
+    ids, counted, before, after = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
+    cap = int(crossed_cap)
+    slots = torch.empty(cap, dtype=torch.int32, device=dev) if cap > 0 else None
+    empty = torch.empty(0, dtype=torch.int32, device=dev)
+    if n == 0:
+        return dmap.size(), 0, False, empty, ids, counted, before, after, 0, 0
+    result = torch.empty(11, dtype=torch.int64, device=dev)
+    own = not eng._stream_ptr(stream)       # as in tally_into_map_device
+    if own:
+        torch.cuda.synchronize(dev)
+    dmap.vote_device(digests, voter, ids, result, scope=scope, threshold=quorum, counted=counted, before=before,
+                     after=after, crossed_slots=slots, stream=stream)
+    if own or not hasattr(stream, "synchronize"):
+        torch.cuda.synchronize(dev)
+    else:
+        stream.synchronize()
+    _, entries, added, full, _, listed, _, _, _, repeats, bad = (int(x) for x in result.cpu().tolist())
+    return (entries, added, bool(full), slots[:listed] if cap > 0 else empty, ids, counted, before, after,
+            repeats, bad)
 
 
 def dedupe_digests_device(hasher: GPUHasher, digests, stream=None):
